@@ -2,10 +2,20 @@
 """Benchmark of the Darknet hot path on MI355X (BASELINE.json: "images/sec YOLOv3-608 train fp16 @1/2/4/8 GPU; detect
 fp16/int8 FPS").
 
-    python bench.py --gpus N --steps K --warmup W [--mode both|train|detect] [--precision fp16|fp32|int8]
+    python bench.py --gpus N --steps K --warmup W [--mode both|train|detect] [--precision fp16|fp32|int8] [--full]
+                    [--dump-outputs DIR]
 
 Default (--mode both): the headline `value` is the TRAINING step (configs[2] shape: YOLOv3-608, batch 64 per GPU, fp16
-autocast with fp32 master weights) and the detection leg (configs[1]: forward + NMS) rides along under "detect".
+autocast with fp32 master weights).  A plain run does only what that figure needs: set up, W warm-up steps, K timed steps,
+the outputs (--dump-outputs) and the result line.  --full adds everything else the line carries: the detection leg
+(configs[1]: forward + NMS) under "detect", the int8 and YOLOv4-640 detection riders, the per-kernel roofline tables, the
+NMS legs and the CPU baselines (each described below).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its LAST step as DIR/<name>.npy (float32):
+for the training step the loss items, the three raw heads, the updated parameters, their gradients and the BatchNorm running
+statistics; for the detection step the detections of every frame.  An array of more than 2^20 values (4 x 2^20 for the
+parameters, gradients, statistics and detections) is written as a fixed, seeded sample of that many values; about 45 MB in
+all.  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 * train step = train-mode forward (batch-statistics BatchNorm) + compute_loss on synthetic labels + backward + GradScaler
   + nesterov SGD (reference train.py:371-433), all convolution / BatchNorm / activation work on libyolo_hip.so.
@@ -18,7 +28,7 @@ autocast with fp32 master weights) and the detection leg (configs[1]: forward + 
 
 Synthetic data and random-init weights (no network access).  Timing: W warm-up steps, then exactly K steps bracketed
 by barrier + synchronize on both sides, MAX over ranks (engine/distutil.py).  Rank 0 prints ONE JSON line; besides the
-driver contract it carries
+driver contract it carries roofline_net, and with --full
   roofline      the dominant kernel class of the measured step (per-op HIP events recorded by the native plan executor
                 on the launch stream): algorithmic conv FLOPs / summed duration against the 2.5 PFLOP/s dense fp16 peak,
                 plus the per-kernel-class table of the step;
@@ -116,6 +126,50 @@ def model_label(cfg, size):
 def model_family(cfg):
     base = os.path.splitext(os.path.basename(cfg))[0]
     return {'yolov3': 'YOLOv3 Darknet-53', 'yolov4': 'YOLOv4 CSPDarknet53 + Mish + SPP/PAN'}.get(base, base)
+
+
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: values per array above which a seeded sample is written (heads: 3 x 4 MB)
+
+
+def dump_array(out_dir, name, t, k=DUMP_SAMPLE, seed=0):
+    """out_dir/<name>.npy in float32: the whole tensor when it holds at most `k` values, else `k` of its values at sorted flat
+    indices drawn from a generator seeded with `seed` (the same indices for every build, given the same shape)."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > k:
+        idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+        t = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
+def dump_train_outputs(out_dir, model, state):
+    """What the last training step handed its caller: the loss items and raw heads, and its effect on the model - the updated
+    parameters, their gradients and the BatchNorm running statistics, each flattened in named_parameters / named_buffers order."""
+    os.makedirs(out_dir, exist_ok=True)
+    dump_array(out_dir, 'loss_items', state['loss'])
+    pred = state['pred']
+    for i, p in enumerate(pred if isinstance(pred, (list, tuple)) else [pred]):
+        dump_array(out_dir, 'head%d' % i, p, seed=1 + i)
+    params = [p for _, p in model.named_parameters()]
+    stats = [b for k, b in model.named_buffers() if k.endswith('running_mean') or k.endswith('running_var')]
+    with torch.no_grad():
+        dump_array(out_dir, 'params', torch.cat([p.reshape(-1).float() for p in params]), k=4 * DUMP_SAMPLE, seed=10)
+        dump_array(out_dir, 'grads', torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                                                for p in params]), k=4 * DUMP_SAMPLE, seed=11)
+        if stats:
+            dump_array(out_dir, 'bn_running_stats', torch.cat([b.reshape(-1).float() for b in stats]), k=4 * DUMP_SAMPLE, seed=12)
+
+
+def dump_detect_outputs(out_dir, result):
+    """What the last detection step handed its caller: detect.py's per-frame detections (x1, y1, x2, y2, conf, cls) as one
+    (M, 7) array with the frame index in front; with --no-nms the decoded (N, rows, 5 + nc) tensor."""
+    os.makedirs(out_dir, exist_ok=True)
+    if torch.is_tensor(result):
+        dump_array(out_dir, 'decoded', result, seed=2)
+        return
+    rows = [torch.cat((torch.full((d.shape[0], 1), float(i), device=d.device), d.float()), 1)
+            for i, d in enumerate(result) if d is not None]
+    dump_array(out_dir, 'detections', torch.cat(rows) if rows else torch.zeros(0, 7), k=4 * DUMP_SAMPLE, seed=3)
 
 
 def build_model(cfg, size, precision, device):
@@ -352,6 +406,7 @@ def train_main(args, device, dist, world, rank, local_rank):
     fp16 = args.precision == 'fp16'
     scaler = torch.amp.GradScaler('cuda', enabled=fp16)
     state = {}
+    keep = rank == 0 and args.dump_outputs is not None
 
     def step():
         with torch.autocast('cuda', dtype=torch.float16, enabled=fp16):
@@ -363,6 +418,8 @@ def train_main(args, device, dist, world, rank, local_rank):
         scaler.step(opt)
         scaler.update()
         state['loss'] = items
+        if keep:
+            state['pred'] = pred
 
     for _ in range(args.warmup):
         step()
@@ -370,6 +427,8 @@ def train_main(args, device, dist, world, rank, local_rank):
     if eng is None:
         raise SystemExit('the HIP training path did not engage (cfg not lowered?)')
     elapsed = distutil.timed_region(step, args.steps, dist, device)
+    if keep:
+        dump_train_outputs(args.dump_outputs, core, state)
     if rank == 0:
         images = world * args.batch * args.steps
         value = images / elapsed
@@ -394,8 +453,10 @@ def train_main(args, device, dist, world, rank, local_rank):
             'roofline_net': {'bound': 'mfma', 'achieved': round(net, 2), 'peak': peak, 'unit': 'TFLOP/s',
                              'frac': round(net / peak, 4), 'per': 'GPU, whole step incl. loss, optimizer and host gaps'},
         }
-        out['roofline'] = train_roofline(eng, x, args.precision)
-        out['cpu_baseline'] = None if (world > 1 or args.no_cpu_baseline) else cpu_train_baseline(args.cfg, args.cpu_seconds, args.size)
+        if args.full:
+            out['roofline'] = train_roofline(eng, x, args.precision)
+        out['cpu_baseline'] = None if (world > 1 or args.no_cpu_baseline or not args.full) \
+            else cpu_train_baseline(args.cfg, args.cpu_seconds, args.size)
     else:
         out = None
     distutil.barrier(dist)
@@ -643,6 +704,11 @@ def main():
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'], help='nccl = RCCL over xGMI (the product path)')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous / timing contract only, on CPU over gloo: no kernels run, the value is meaningless')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline step: the detection riders (fp16, int8, YOLOv4-640), the per-kernel roofline '
+                         'tables, the NMS legs and the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'RANK' not in os.environ:
@@ -693,12 +759,15 @@ def main():
             if dist is not None:
                 dist.destroy_process_group()
             return
-    if args.mode in ('detect', 'both'):
+    if args.mode == 'detect' or (args.mode == 'both' and args.full):
+        import copy
         keys = ('metric', 'value', 'unit', 'ms_per_step', 'dtype', 'config', 'roofline_net', 'roofline', 'nms', 'nms_test_settings')
 
         def rider(name, rargs, eval_nms=False):
             """A detection leg that rides on the headline line; detect_main raises on every rank together, so catching here
             keeps the ranks in step."""
+            rargs = copy.copy(rargs)
+            rargs.dump_outputs = None        # the outputs are the headline step's
             try:
                 d = detect_main(rargs, device, dist, world, rank, cpu_baseline_leg=False, eval_nms=eval_nms)
                 if rank == 0 and d is not None:
@@ -714,7 +783,6 @@ def main():
         else:
             rider('detect', args, eval_nms=True)      # the second headline metric of BASELINE.json, measured in the same run
         if args.mode == 'both' and args.precision == 'fp16':
-            import copy
             # third headline metric ("detect int8 FPS"): the COS-PTQ graph on the MFMA-i8 engine, same frames, same NMS
             iargs = copy.copy(args)
             iargs.precision = 'int8'
@@ -737,6 +805,7 @@ def main():
             targs = copy.copy(args)
             targs.cfg, targs.size, targs.batch = os.path.join(PKG, 'cfg', *rel.split('/')), size, min(args.batch, batch)
             targs.steps, targs.warmup, targs.no_cpu_baseline = min(args.steps, 10), min(args.warmup, 3), True
+            targs.full, targs.dump_outputs = True, None      # the rider reports its roofline; the outputs are the headline's
             try:
                 t = train_main(targs, device, dist, world, rank, local_rank)
                 r = t.get('roofline') or {}
@@ -873,21 +942,28 @@ def detect_main(args, device, dist, world, rank, cpu_baseline_leg=True, eval_nms
     if not all_ranks_ok(err is None, dist, device):
         raise err if err is not None else RuntimeError('detect leg failed on another rank')
 
+    last = {}
+    keep = rank == 0 and args.dump_outputs is not None
+
     def step():      # detect.py's loop body (this package's detect.py: model.hip_detect = forward + NMS as one engine call)
         with torch.no_grad():
             if args.no_nms:
-                model(x)
+                res = model(x)[0]
             elif args.two_pass_nms:
                 inf, _, _ = model(x)
-                non_max_suppression(inf, conf_thres=0.3, iou_thres=0.6, multi_label=False)
+                res = non_max_suppression(inf, conf_thres=0.3, iou_thres=0.6, multi_label=False)
             else:
-                model.hip_detect(x, conf_thres=0.3, iou_thres=0.6, multi_label=False)
+                res = model.hip_detect(x, conf_thres=0.3, iou_thres=0.6, multi_label=False)
+        if keep:
+            last['out'] = res
 
     from engine import distutil
     for _ in range(args.warmup):
         step()
     # barrier + synchronize on both sides of exactly K steps; MAX over ranks (engine/distutil.py)
     elapsed = distutil.timed_region(step, args.steps, dist, device)
+    if keep:
+        dump_detect_outputs(args.dump_outputs, last['out'])
 
     if rank == 0:
         images = world * args.batch * args.steps
@@ -913,7 +989,7 @@ def detect_main(args, device, dist, world, rank, cpu_baseline_leg=True, eval_nms
             'roofline_net': {'bound': 'mfma', 'achieved': round(net_tflops, 2), 'peak': peak, 'unit': 'TFLOP/s',
                              'frac': round(net_tflops / peak, 4), 'per': 'GPU, whole step incl. NMS and host gaps'},
         }
-        if not args.no_nms:
+        if args.full and not args.no_nms:
             with torch.no_grad():
                 inf, _, _ = model(x)
             out['nms'] = nms_leg(inf, max(3, min(args.steps, 10)))
@@ -922,8 +998,9 @@ def detect_main(args, device, dist, world, rank, cpu_baseline_leg=True, eval_nms
                     out['nms_test_settings'] = nms_test_settings_leg(inf, size=args.size)
                 except Exception as e:       # a rider never takes the line down
                     out['nms_test_settings'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        out['roofline'] = roofline_leg(model, x, max(3, min(args.steps, 10)), args.precision)
-        if world == 1 and not args.no_cpu_baseline and cpu_baseline_leg:
+        if args.full:
+            out['roofline'] = roofline_leg(model, x, max(3, min(args.steps, 10)), args.precision)
+        if args.full and world == 1 and not args.no_cpu_baseline and cpu_baseline_leg:
             out['cpu_baseline'] = cpu_baseline(args.cfg, args.size, args.cpu_seconds)
         else:
             out['cpu_baseline'] = None

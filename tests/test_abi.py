@@ -1,5 +1,6 @@
 """The shared library must load without a GPU and export exactly the C ABI that include/yolo_hip.h declares."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -120,3 +121,36 @@ def test_kernel_selection_on_the_headline_network():
     bad = _conv(F16, 64, 304, 32, 48, 3, 1)
     bad.tile = 72
     assert lib.yh_conv2d_fwd(C.byref(bad), None) != 0
+
+
+def _roll_workspace(r):
+    """Floats of partial tiles conv_wgrad_roll_kernel writes for a 3x3 / s1 row (csrc/conv_wgrad_roll.hip, wgrad_roll_geometry): one
+    128 x [9 x 64] tile per (split, tile); 256 / tiles splits of the 32-position steps of the padded pixel space, at least 8 steps each."""
+    tiles = (r['cout'] // 128) * (r['cin'] // 64)
+    steps = -(-r['n'] * (r['h'] + 1) * (r['w'] + 1) // 32)
+    splits = max(1, min(256 // tiles, steps // 8))
+    per_split = -(-steps // splits)
+    return -(-steps // per_split) * tiles * 128 * 576
+
+
+def test_wgrad_kernel_selection_is_pinned():
+    """Which weight-gradient kernel every conv layer of every shipped cfg runs on, and the workspace it asks for, against the table
+    recorded before the superseded forms (round-3 halo kernel, 128 x 256 / 256 x 256 im2col tiles) were deleted
+    (tests/golden/make_golden_wgrad_selection.py; yh_conv2d_wgrad_kernel / _workspace are host code).  Rows whose `halo` flag is set
+    had their workspace sized by the deleted kernel's geometry where that was the larger: they run on the rolling form (91), and
+    the workspace must cover what that form writes."""
+    lib = hiplib.load()
+    rows = json.load(open(os.path.join(REPO, 'tests', 'golden', 'wgrad_selection.json')))
+    assert len(rows) > 300 and {r['kernel'] for r in rows} == {1, 22, 42, 82, 91}
+    for r in rows:
+        pad, k, s = r['pad'], r['k'], r['stride']
+        d = hiplib.WgradDesc(n=r['n'], h=r['h'], w_in=r['w'], cin=r['cin'], ho=(r['h'] + 2 * pad - k) // s + 1, wo=(r['w'] + 2 * pad - k) // s + 1,
+                             cout=r['cout'], kh=k, kw=k, stride=s, pad=pad, ldx=r['cin'], lddz=-(-r['cout'] // 8) * 8, dtype=r['dtype'], splits=0,
+                             cin_w=r['cin_w'])
+        d.x = d.dz = d.dw = 4096          # any aligned non-null address: the pickers read no memory
+        assert lib.yh_conv2d_wgrad_kernel(C.byref(d)) == r['kernel'], r
+        ws = lib.yh_conv2d_wgrad_workspace(C.byref(d))
+        if r['halo']:
+            assert r['kernel'] == 91 and _roll_workspace(r) <= ws <= r['workspace'], (r, ws)
+        else:
+            assert ws == r['workspace'], (r, ws)

@@ -173,27 +173,26 @@ def test_wgrad_row_tiles_agree(libs, monkeypatch, case, bm, use_ws):
     assert torch.equal(got.cpu(), ref)
 
 
-@pytest.mark.parametrize('mode', ['1', '2', '3'], ids=['halo', 'auto', 'roll'])
+@pytest.mark.parametrize('draw', [1, 0, 2], ids=['halo', 'auto', 'roll'])
 @pytest.mark.parametrize('wgs', ['', '4', '64'], ids=['auto', 'few_splits', 'many_splits'])
 @pytest.mark.parametrize('case', [(2, 21, 19, 64, 256), (7, 16, 40, 32, 512), (1, 76, 76, 128, 256), (3, 33, 152, 32, 256),
                                   (2, 23, 17, 128, 128), (1, 9, 152, 64, 128), (1, 5, 190, 64, 384), (9, 4, 16, 192, 128)],
                          ids=lambda c: 'n%d_%dx%d_c%d-%d' % c)
-def test_wgrad_halo_form_is_exact_on_small_integers(libs, monkeypatch, case, wgs, mode):
-    """The 3x3 halo weight-gradient kernels on integer operands: every product and partial sum exact, so any mistake in the pad
-    handling, the tap offsets, the split ranges or the partial-tile reduction shows as a wrong integer.  mode 1: conv_wgrad_halo_kernel
-    (csrc/conv_wgrad.hip: one shared pad row / column, dz in virtual pixel order, halo image read as nine shifted views; cout % 256,
-    cin % 32); mode 3: conv_wgrad_roll_kernel wherever it qualifies (csrc/conv_wgrad_roll.hip: 128 x [9 x 64] tile, x rows rolling
-    through a 512-row ring; cout % 128, cin % 64); mode 2 (the default): the library's per-layer choice between the two - a case one
-    form does not take runs on the next form down, which must be just as exact.  Ragged last
-    chunks / steps, split counts that do not divide, W = 152 and 190 (the shortest dz rings), images smaller than one 32-position step."""
+def test_wgrad_halo_form_is_exact_on_small_integers(libs, monkeypatch, case, wgs, draw):
+    """The 3x3 / stride 1 weight gradient on integer operands: every product and partial sum exact, so any mistake in the pad
+    handling, the tap offsets, the split ranges or the partial-tile reduction shows as a wrong integer.  The library's one choice:
+    conv_wgrad_roll_kernel wherever it qualifies (csrc/conv_wgrad_roll.hip: 128 x [9 x 64] tile, x rows rolling through a 512-row
+    ring, one shared pad row / column; cout % 128, cin % 64); the cin = 32 cases do not qualify and run on the im2col two-stage
+    form, which must be just as exact.  Ragged last steps, split counts that do not divide, W = 152 and 190 (the shortest dz
+    rings), images smaller than one 32-position step.  `draw`: three independent draws of the operands per case; their ids are
+    those of the three kernel modes (YH_WGRAD_HALO = 1 / 2 / 3) this test selected before the library had one choice."""
     if DRY:
         pytest.skip('kernel-only property')
     lib, _ = libs
-    monkeypatch.setenv('YH_WGRAD_HALO', mode)
     if wgs:
         monkeypatch.setenv('YH_WGRAD_HALO_WGS', wgs)
     N, H, W, cin, cout = case
-    g = torch.Generator().manual_seed(sum(case))
+    g = torch.Generator().manual_seed(sum(case) + 1000 * draw)
     x = torch.randint(-3, 4, (N, H, W, cin), generator=g).half()
     dz = torch.randint(-2, 3, (N, H, W, cout), generator=g).half()
     got = oh.wgrad(lib, F16, x.to(GPU), dz.to(GPU), cin, cout, 3, 1, 1, use_ws=True)
@@ -202,24 +201,22 @@ def test_wgrad_halo_form_is_exact_on_small_integers(libs, monkeypatch, case, wgs
     assert torch.equal(got.cpu(), ref)
 
 
-@pytest.mark.parametrize('mode,kernel', [('1', 90), ('3', 91)], ids=['halo', 'roll'])
 @pytest.mark.parametrize('case', [(2, 21, 19, 64, 256), (1, 76, 76, 128, 256), (3, 38, 38, 256, 512), (3, 33, 120, 64, 256)],
                          ids=lambda c: 'n%d_%dx%d_c%d-%d' % c)
-def test_wgrad_halo_form_matches_autograd_on_random_operands(libs, monkeypatch, case, mode, kernel):
-    """the halo kernels against torch autograd DIRECTLY (float64 conv2d weight gradient of the same f16
+def test_wgrad_halo_form_matches_autograd_on_random_operands(libs, case):
+    """the rolling-halo kernel against torch autograd DIRECTLY (float64 conv2d weight gradient of the same f16
     operands), random - not small-integer - values: products exact in fp32, accumulation order the only difference (<= 1e-4 of the
     gradient's scale, the bound of the im2col form in test_wgrad_matches_autograd)."""
     if DRY:
         pytest.skip('kernel-only property')
     lib, _ = libs
-    monkeypatch.setenv('YH_WGRAD_HALO', mode)
     N, H, W, cin, cout = case
     g = torch.Generator().manual_seed(sum(case) + 1)
     x = (torch.randn(N, H, W, cin, generator=g) * 0.7).half()
     dz = (torch.randn(N, H, W, cout, generator=g) * 0.05).half()
     d = oh.WgradDesc(n=N, h=H, w_in=W, cin=cin, ho=H, wo=W, cout=cout, kh=3, kw=3, stride=1, pad=1, ldx=cin, lddz=cout, dtype=F16, splits=0)
     d.x = d.dz = d.dw = 4096
-    assert lib.yh_conv2d_wgrad_kernel(oh.C.byref(d)) == kernel, 'the case must run on the kernel under test'
+    assert lib.yh_conv2d_wgrad_kernel(oh.C.byref(d)) == 91, 'the case must run on the kernel under test'
     got = oh.wgrad(lib, F16, x.to(GPU), dz.to(GPU), cin, cout, 3, 1, 1, use_ws=True).cpu().double()
     ref = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (cout, cin, 3, 3), dz.double().permute(0, 3, 1, 2), padding=1)
     err = (got - ref).abs().max().item()
@@ -227,13 +224,12 @@ def test_wgrad_halo_form_matches_autograd_on_random_operands(libs, monkeypatch, 
 
 
 @pytest.mark.parametrize('case', [(2, 17, 23, 64, 128, 32, 16), (1, 20, 31, 128, 256, 64, 128)], ids=lambda c: 'n%d_%dx%d_c%d-%d_x%d_z%d' % c)
-def test_wgrad_roll_form_reads_pitched_channel_slices(libs, monkeypatch, case):
+def test_wgrad_roll_form_reads_pitched_channel_slices(libs, case):
     """conv_wgrad_roll_kernel on operands that are channel slices of wider buffers (route / concat outputs: ldx > cin, lddz > cout,
     non-zero first channel), exact on integers; the surrounding channels hold large values that must not be read."""
     if DRY:
         pytest.skip('kernel-only property')
     lib, _ = libs
-    monkeypatch.setenv('YH_WGRAD_HALO', '3')
     N, H, W, cin, cout, xe, ze = case
     g = torch.Generator().manual_seed(sum(case))
     x = torch.randint(-3, 4, (N, H, W, cin + 2 * xe), generator=g).half()

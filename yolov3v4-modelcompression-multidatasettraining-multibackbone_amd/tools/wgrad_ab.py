@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""A/B of the weight-gradient kernels on the layer shapes of a training step (one process, same box): for every shape, each mode of
-YH_WGRAD_HALO (1 = conv_wgrad_halo_kernel, 2 = conv_wgrad_roll_kernel) is checked against mode 0 (im2col kernels) on random operands
-and timed with HIP events over `--reps` back-to-back launches (kernel + its reduce launch).
+"""Timing of the weight-gradient kernels on the layer shapes of a training step (one process, same box): for every shape, the
+library's choice - and every `--variants` setting of the remaining knobs (YH_WGRAD_BM, YH_WGRAD_HALO_WGS) - is checked against
+torch.nn.grad.conv2d_weight in float64 on random operands and timed with HIP events over `--reps` back-to-back launches (kernel + its
+reduce launch).
 
-    python tools/wgrad_ab.py [--batch 64] [--reps 20] [--shapes yolov3] [--env K=V ...variants]
+    python tools/wgrad_ab.py [--batch 64] [--reps 40] [--shapes yolov3] [--variants K=V[,K=V] ...]
 """
 import argparse
 import ctypes as C
@@ -36,8 +37,8 @@ def main():
     ap.add_argument('--reps', type=int, default=40)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--shapes', default='yolov3')
-    ap.add_argument('--variants', nargs='*', default=['YH_WGRAD_HALO=1', 'YH_WGRAD_HALO=2'],
-                    help='environment settings to compare, comma-separated K=V lists, e.g. YH_WGRAD_HALO=2,YH_WGRAD_ROLL_STAGES=6')
+    ap.add_argument('--variants', nargs='*', default=[],
+                    help='environment settings to time next to the default, comma-separated K=V lists, e.g. YH_WGRAD_BM=128 YH_WGRAD_HALO_WGS=128')
     ap.add_argument('--no-check', action='store_true')
     args = ap.parse_args()
     lib = hiplib.load()
@@ -51,27 +52,22 @@ def main():
         flops = 2.0 * N * H * W * cin * cout * k * k
         ref = None
         if not args.no_check:
-            os.environ['YH_WGRAD_HALO'] = '0'
-            ref = oh.wgrad(lib, hiplib.YH_F16, x, dz, cin, cout, k, 1, (k - 1) // 2)
-            torch.cuda.synchronize()
+            ref = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (cout, cin, k, k), dz.double().permute(0, 3, 1, 2), padding=(k - 1) // 2)
         setups = []
-        for var in args.variants:
-            sets = dict(kv.split('=') for kv in var.split(','))
+        for var in [''] + args.variants:
+            sets = dict(kv.split('=') for kv in var.split(',')) if var else {}
             set_env(sets)
-            stamps = int(sets.get('YH_WGRAD_ROLL_ABL', '0')) & 8 != 0      # s_memtime sums of one workgroup behind the partial tiles
             dw = torch.zeros((cout, cin, k, k), device=dev, dtype=torch.float32)
             d = oh.WgradDesc(x=oh.P(x), dz=oh.P(dz), dw=oh.P(dw), n=N, h=H, w_in=W, cin=cin, ho=H, wo=W, cout=cout, kh=k, kw=k,
                              stride=1, pad=(k - 1) // 2, ldx=cin, lddz=cout, dtype=hiplib.YH_F16, splits=0)
             need = int(lib.yh_conv2d_wgrad_workspace(C.byref(d)))
-            ws = torch.zeros((max(need, 1) + 64,), device=dev, dtype=torch.float32)
-            d.ws, d.ws_floats = oh.P(ws), need + (64 if stamps else 0)
+            ws = torch.zeros((max(need, 1),), device=dev, dtype=torch.float32)
+            d.ws, d.ws_floats = oh.P(ws), need
             code = int(lib.yh_conv2d_wgrad_kernel(C.byref(d)))
             oh.call(lib, 'yh_conv2d_wgrad', d)
             torch.cuda.synchronize()
-            err = float('nan')
-            if ref is not None and int(sets.get('YH_WGRAD_ROLL_ABL', '0')) & 7 == 0:
-                err = ((dw - ref).abs().max() / ref.abs().max()).item()
-            setups.append(dict(var=var, sets=sets, d=d, dw=dw, ws=ws, need=need, code=code, err=err, stamps=stamps, ms=[]))
+            err = float('nan') if ref is None else ((dw.double() - ref).abs().max() / ref.abs().max()).item()
+            setups.append(dict(var=var or 'default', sets=sets, d=d, dw=dw, ws=ws, code=code, err=err, ms=[]))
         # interleaved rounds: the clock / thermal state drifts over a run by more than the differences looked for (the same kernel
         # measured 0.26 and 0.23 ms at the start and the end of one process), so every variant is timed once per round
         for rnd in range(args.rounds):
@@ -87,18 +83,11 @@ def main():
                 torch.cuda.synchronize()
                 su['ms'].append(e0.elapsed_time(e1) / args.reps)
         for su in setups:
-            if su['stamps']:
-                t = su['ws'][su['need']:su['need'] + 48].view(torch.int64).cpu().view(3, 8)
-                names = ('reads', 'barrier1', 'mfma', 'barrier2', 'wait+roll', 'barrier3', 'issue')
-                for gq in range(3):
-                    ns = max(int(t[gq, 7]), 1)
-                    print('    group %d (%d steps), cycles per step: %s  total %d' % (gq, ns, '  '.join('%s %d' % (nm, int(t[gq, kk]) // ns) for kk, nm in enumerate(names)),
-                                                                                 sum(int(t[gq, kk]) for kk in range(7)) // ns))
             ms = sorted(su['ms'])
             med = ms[len(ms) // 2]
             print('%-28s %-52s %9.4f %9.4f %9.1f %10.2e' % ('%dx%d %d->%d k%d b%d' % (H, W, cin, cout, k, N), '%s [kernel %d]' % (su['var'], su['code']),
                                                            med, ms[0], flops / med / 1e9, su['err']), flush=True)
-        del x, dz
+        del x, dz, ref
         torch.cuda.empty_cache()
 
 

@@ -513,6 +513,25 @@ typedef struct yh_pack_item {
 } yh_pack_item;
 int yh_pack_batch(const yh_pack_item* items, int n_items, void* stream);
 
+/* Network-slimming sparsity term (csrc/sparsity.hip): the subgradient of s * sum |gamma| added to the gradients of the BatchNorm
+ * gammas under the L1 penalty, all layers in ONE launch.  Replaces `BNOptimizer.updateBN(sr_flag, model.module_list, opt.s,
+ * prune_idx)` after `loss.backward()` (reference train.py:443-448, utils/prune_utils.py:130-138: per layer
+ * `bn.weight.grad.data.add_(s * torch.sign(bn.weight.data))`, three small launches each).
+ *   rows    DEVICE array of rows; gamma / grad are fp32, 16-byte aligned at their start, n >= 1 elements (any n: the tail of a
+ *           row is neither read nor written past n); gamma and grad of one row may not overlap other rows' grad
+ *   [first, last)  the rows this call serves (a backward range of the training plan); first == last: YH_OK, nothing is launched
+ *   s       the penalty weight; may change from call to call, the table does not
+ * For every element: grad[i] = grad[i] + (s * sign(gamma[i])) with torch.sign's values ((0 < x) - (x < 0): +0, -0 and NaN give 0), the
+ * product rounded to fp32 before the add - the bits of `grad.add_(s * torch.sign(gamma))`.  No atomics, no LDS, no workspace.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+typedef struct yh_bn_l1_row {
+    const float* gamma;     /* the live BatchNorm weight                                                        */
+    float* grad;            /* its gradient (engine: the slice of the plan's gradient arena)                    */
+    int32_t n;              /* channels                                                                         */
+    int32_t reserved;       /* 0                                                                                */
+} yh_bn_l1_row;
+int yh_bn_l1_subgrad(const yh_bn_l1_row* rows, int first, int last, float s, void* stream);
+
 typedef struct yh_wgrad_desc {
     const void* x;          /* forward input of the conv, NHWC dtype (stem: NCHW fp32 image)                    */
     const void* dz;         /* gradient of the conv output, NHWC dtype, pitch lddz                              */

@@ -191,6 +191,10 @@ class PackBatchDesc(C.Structure):
     _fields_ = [('items', _vp), ('n_items', _i32)]
 
 
+class BnL1Row(C.Structure):
+    _fields_ = [('gamma', _vp), ('grad', _vp), ('n', _i32), ('reserved', _i32)]
+
+
 class DwBwdDesc(C.Structure):
     _fields_ = [('x', _vp), ('dz', _vp), ('w', _vp), ('dx', _vp), ('dw', _vp),
                 ('n', _i32), ('h', _i32), ('w_in', _i32), ('c', _i32), ('ho', _i32), ('wo', _i32), ('k', _i32), ('stride', _i32),
@@ -292,6 +296,7 @@ _SIGNATURES = {
     'yh_cast_f32': (C.c_int, [C.POINTER(CastDesc), _vp]),
     'yh_maxpool2d_bwd': (C.c_int, [C.POINTER(PoolBwdDesc), _vp]),
     'yh_pack_batch': (C.c_int, [_vp, C.c_int, _vp]),
+    'yh_bn_l1_subgrad': (C.c_int, [_vp, C.c_int, C.c_int, _f32, _vp]),
     'yh_dw_wgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),
     'yh_dw_wgrad_workspace': (_i64, [C.POINTER(DwBwdDesc)]),
     'yh_dw_dgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),

@@ -331,6 +331,13 @@ class PaddedTrainEngine:
     def _get_plan(self, x):
         return self.inner._get_plan(x)
 
+    def set_bn_sparsity(self, block_indices, s):
+        """The twin has the model's blocks one for one, so the set carries over.  The term s * sign(gamma) is added in the TWIN's
+        gradient arena (``TrainEngine.backward_segment``), before ``map_grads`` gathers the real lanes back: pad lanes hold
+        gamma = 0 exactly (``push`` fills them from the zero slot), sign(0) = 0, so their term is exactly 0 - and they are not
+        gathered anyway."""
+        self.inner.set_bn_sparsity(block_indices, s)
+
     def parameters(self):
         return list(self.pad.real_params)
 

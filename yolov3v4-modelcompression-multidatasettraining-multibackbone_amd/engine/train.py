@@ -38,7 +38,7 @@ import torch.nn as nn
 from . import hiplib
 from .hiplib import (ConvDesc, StemDesc, CopyDesc, AddDesc, BnStatsDesc, BnFinalizeDesc, BnActFwdDesc, BnBwdReduceDesc,
                      BnBwdApplyDesc, WgradDesc, StemWgradDesc, StemBwdDesc, UpsampleBwdDesc, CastDesc, LayoutDesc, PoolDesc, PoolBwdDesc, PackItem, PackBatchDesc, DwDesc, SeDesc, DwWgradDesc,
-                     DwDgradDesc, SeBwdDesc)
+                     DwDgradDesc, SeBwdDesc, BnL1Row)
 from .plan import DarknetEngine, ALIGN_C, _round_up
 
 # stride-2 data gradients with at most this many input channels run as ONE four-phase pass (ups = 4: 16 tap-GEMMs instead of 9, dz read
@@ -90,6 +90,8 @@ class TrainEngine(DarknetEngine):
         self._tplans = {}
         self._current = None
         self.steps = 0   # forward count; the autograd node checks it so a stale backward fails loudly
+        self._l1_blocks = ()   # network-slimming sparsity: blocks whose BatchNorm gamma carries the L1 penalty (set_bn_sparsity)
+        self._l1_s = 0.0
 
     # --------------------------------------------------------------------------------- parameters
     def parameters(self):
@@ -163,6 +165,73 @@ class TrainEngine(DarknetEngine):
             raise RuntimeError('pack table size changed: rebuild the plan')
         plan['pack_table'].copy_(host)
         plan['pack_ptrs'] = ptrs
+
+    # --------------------------------------------------------------------------------- sparsity (network slimming)
+    def set_bn_sparsity(self, block_indices, s):
+        """L1 penalty s * sum |gamma| on the BatchNorm gammas of the cfg blocks ``block_indices`` (reference train.py:443-448 calls
+        ``BNOptimizer.updateBN`` after every backward, utils/prune_utils.py:130-138): every backward range adds s * sign(gamma) to the
+        gradients of its rows with one ``yh_bn_l1_subgrad`` launch, before the gradients are handed to autograd.  ``s`` may change
+        from step to step (it is a launch argument, not part of the table); ``None`` / an empty list switches the term off."""
+        blocks = tuple(sorted({int(b) for b in block_indices})) if block_indices is not None else ()
+        if blocks:
+            have = {}
+            for i, block in enumerate(self.model.module_list):
+                if isinstance(block, nn.Sequential) and len(block) and isinstance(block[0], nn.Conv2d):
+                    have[i] = any(isinstance(k, nn.modules.batchnorm.BatchNorm2d) for k in list(block.children())[1:])
+            bad = [b for b in blocks if not have.get(b, False)]
+            if bad:
+                raise ValueError('set_bn_sparsity: blocks %s are not conv blocks with BatchNorm' % bad)
+        if blocks != self._l1_blocks:
+            self._l1_blocks = blocks
+            for plan in self._tplans.values():
+                plan['l1_key'] = None         # rewritten before the next forward
+        self._l1_s = float(s) if blocks else 0.0
+
+    def _l1_values(self, plan):
+        """The values whose gamma is a row, in ``parameters()`` order (= value order), with the backward range each belongs to."""
+        want = set(self._l1_blocks)
+        out = []
+        for k, seg in enumerate(plan['segments']):
+            lo, hi = seg['values']
+            for v in plan['values'][lo:hi]:
+                if v.kind in ('conv', 'dw') and v.bn is not None and v.block in want:
+                    out.append((k, v))
+        return out
+
+    def _refresh_l1_table(self, plan):
+        """(Re)write the device table of yh_bn_l1_row when the set changed or a gamma moved (plan build, ``param.data = ...``): the
+        condition of ``_refresh_pack_table``.  Row r: the live gamma, its slice of the plan's gradient arena, its width."""
+        if not self._l1_blocks:
+            plan['l1_key'], plan['l1_ranges'] = None, None
+            return
+        rows = self._l1_values(plan)
+        key = (self._l1_blocks, tuple(v.bn.weight.data_ptr() for _, v in rows))
+        if plan.get('l1_key') == key:
+            return
+        missing = set(self._l1_blocks) - {v.block for _, v in rows}
+        if missing:
+            raise RuntimeError('set_bn_sparsity: blocks %s have no BatchNorm gradient in the training plan' % sorted(missing))
+        grads = plan['grads']
+        items = []
+        for _, v in rows:
+            g = v.bn.weight
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                raise NotImplementedError('HIP training path: BatchNorm tensors must be contiguous fp32')
+            items.append(BnL1Row(gamma=g.data_ptr(), grad=grads.ptr(v.g_gamma), n=v.C))
+        raw = bytes((BnL1Row * len(items))(*items))
+        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+        table = plan.get('l1_table')
+        if table is None or table.numel() < host.numel():
+            # sized for every BatchNorm of the graph, so a later change of the set rewrites it in place
+            cap = sum(1 for v in plan['values'] if v.kind in ('conv', 'dw') and getattr(v, 'bn', None) is not None)
+            table = plan['l1_table'] = torch.zeros(max(cap, len(items)) * C.sizeof(BnL1Row), device=self.device, dtype=torch.uint8)
+        table[:host.numel()].copy_(host)
+        ranges, r = [], 0
+        for k in range(len(plan['segments'])):
+            n = sum(1 for kk, _ in rows if kk == k)
+            ranges.append((r, r + n))
+            r += n
+        plan['l1_ranges'], plan['l1_key'] = ranges, key
 
     # --------------------------------------------------------------------------------- plans
     def _check_supported(self, values):
@@ -905,6 +974,7 @@ class TrainEngine(DarknetEngine):
             x = x.float()
         plan = self._get_plan(x)
         self._refresh_pack_table(plan)   # the packing itself is op 0 of the forward plan (one launch)
+        self._refresh_l1_table(plan)
         lib = self.lib
         plan['stats'].buf.zero_()
         heads = [torch.empty(shape, device=x.device, dtype=torch.float32) for shape in plan['head_shapes']]
@@ -979,6 +1049,12 @@ class TrainEngine(DarknetEngine):
         if last > first:
             hiplib.check(lib.yh_plan_run_range(plan['bwd'], first, last, hiplib.stream_ptr()), 'yh_plan_run_range(train backward)')
         plan['bwd_next'] = k - 1
+        if plan.get('l1_ranges') is not None:
+            # the sparsity term of this range's gammas: after the ops that wrote their gradients, before the clone below leaves the arena
+            r_lo, r_hi = plan['l1_ranges'][k]
+            if r_hi > r_lo:
+                hiplib.check(lib.yh_bn_l1_subgrad(plan['l1_table'].data_ptr(), r_lo, r_hi, self._l1_s, hiplib.stream_ptr()),
+                             'yh_bn_l1_subgrad')
         p_lo, p_hi = seg['params']
         if p_hi == p_lo:
             return []

@@ -460,6 +460,7 @@ class Darknet(nn.Module):
             # channel-padded twin (engine/padded.py).  NotImplementedError surfaces here, before any state changes
             eng = make_train_engine(self, precision, x)
             self.__dict__['_hip_train_engine'] = eng
+        eng.set_bn_sparsity(*self.__dict__.get('_hip_bn_sparsity', (None, 0.0)))   # survives engine rebuilds: the setting lives here
         plan = eng._get_plan(x)
         heads = [None] * len(self.yolo_layers)
         token = x
@@ -474,6 +475,18 @@ class Darknet(nn.Module):
             bs, ny, nx, _ = h.shape
             yolo_out.append(h[..., :m.na * m.no].view(bs, ny, nx, m.na, m.no).permute(0, 3, 1, 2, 4))
         return yolo_out, []
+
+    def hip_set_bn_sparsity(self, prune_idx, s):
+        """Network-slimming sparse training on the HIP step: the L1 subgradient ``s * sign(gamma)`` of the BatchNorm gammas of the
+        blocks ``prune_idx`` is added to their gradients inside the backward (one launch per backward range, engine/train.py
+        ``set_bn_sparsity``) - what the reference does with ``BNOptimizer.updateBN`` after ``loss.backward()`` (train.py:443-448).
+        ``None`` / an empty list switches it off; ``s`` may change between steps.  Eager (CPU) steps are not affected: the training
+        script applies the same formula in torch there."""
+        idx = tuple(int(i) for i in prune_idx) if prune_idx is not None and len(prune_idx) else None
+        self.__dict__['_hip_bn_sparsity'] = (idx, float(s) if idx else 0.0)
+        eng = self.__dict__.get('_hip_train_engine')
+        if eng is not None:
+            eng.set_bn_sparsity(*self.__dict__['_hip_bn_sparsity'])
 
     def _forward_hip(self, x):
         from engine.plan import DarknetEngine  # raises if libyolo_hip.so is missing: no fallback

@@ -9,8 +9,9 @@ On a GPU the step runs on the HIP training path: ``model(imgs)`` in train mode, 
 
 (``LOCAL_RANK`` / ``WORLD_SIZE`` from the launcher; ``nccl`` = RCCL on GPUs, ``gloo`` on CPU).  Not carried over:
 tensorboard logging, hyper-parameter evolution, cloud buckets, knowledge-distillation strategies 2-5 (1 is kept),
-the FenceMask/GridMask augmentations.  BN-gamma sparsity training (``--prune``/``-s``) uses ``utils.prune_utils`` of a
-reference checkout when one is importable (utils/__init__.py).
+the FenceMask/GridMask augmentations.  BN-gamma sparsity training (``--prune``/``-s``, network slimming) picks its layers with
+``engine/slimming.py``; on a GPU the L1 term is added inside the HIP backward (one launch per backward range), on CPU tensors
+by the same formula in torch.
 """
 import argparse
 import glob
@@ -27,6 +28,7 @@ import torch.optim.lr_scheduler as lr_scheduler
 from torch.utils.data import DataLoader
 
 import test as test_module   # the library function test.test
+from engine.slimming import apply_bn_l1_
 from models import Darknet, attempt_download, load_darknet_weights
 from utils import torch_utils
 from utils.datasets import LoadImagesAndLabels
@@ -93,17 +95,10 @@ def build_optimizer(model, opt, hyp, device):
 
 
 def sparsity_layers(prune, module_defs):
-    """BN layers under the L1 sparsity penalty for --prune 0 / 1 / 2 (reference train.py:237-262)."""
-    from utils.prune_utils import parse_module_defs, parse_module_defs2, parse_module_defs4
-    if prune == 0:      # regular prune: convs outside shortcuts
-        _, _, prune_idx = parse_module_defs(module_defs)
-    elif prune == 1:    # shortcut prune
-        _, _, prune_idx, _, _ = parse_module_defs2(module_defs)
-    elif prune == 2:    # layer prune
-        _, _, prune_idx = parse_module_defs4(module_defs)
-    else:
-        raise ValueError('--prune must be 0, 1 or 2')
-    return prune_idx
+    """BN layers under the L1 sparsity penalty for --prune 0 / 1 / 2 (reference train.py:237-262): regular prune (convs outside
+    shortcuts), shortcut prune, layer prune."""
+    from engine.slimming import sparsity_blocks
+    return sparsity_blocks(module_defs, prune)
 
 
 def train(opt, hyp):
@@ -215,10 +210,14 @@ def train(opt, hyp):
         m.class_weights = labels_to_class_weights(dataset.labels, nc).to(device)
     ema = torch_utils.ModelEMA(core) if opt.ema else None
 
-    prune_idx = None
-    if opt.prune != -1:   # BN-gamma sparsity (network slimming) needs the reference's utils.prune_utils
+    prune_idx, sparsity_in_step = None, False
+    if opt.prune != -1:   # BN-gamma sparsity (network slimming): grad(gamma) += s * sign(gamma) after every backward (train.py:443-448)
         prune_idx = sparsity_layers(opt.prune, core.module_defs)
-        from utils.prune_utils import BNOptimizer
+        # on the HIP step the term is part of the backward (engine/train.py set_bn_sparsity: it reaches DDP's buckets with the gradient,
+        # mean over ranks of (g + t) = mean(g) + t); the eager modules get it from the torch formula below
+        sparsity_in_step = device.type == 'cuda' and opt.quantized == -1
+        if sparsity_in_step:
+            core.hip_set_bn_sparsity(prune_idx, opt.s)
 
     nb = len(dataloader)
     n_burn = max(3 * nb, 500)
@@ -290,8 +289,8 @@ def train(opt, hyp):
 
             loss = loss * (batch_size * (world if distributed else 1) / 64)
             scaler.scale(loss).backward()
-            if prune_idx is not None:
-                BNOptimizer.updateBN(True, core.module_list, opt.s, prune_idx)
+            if prune_idx is not None and not sparsity_in_step:
+                apply_bn_l1_(core.module_list, prune_idx, opt.s)
             if ni % accumulate == 0:
                 scaler.step(optimizer)
                 scaler.update()

@@ -664,6 +664,24 @@ typedef struct yh_letterbox_desc {
 } yh_letterbox_desc;
 int yh_letterbox_fwd(const yh_letterbox_desc* d, void* stream);
 
+/* Multi-scale training (csrc/resize.hip): bilinear resize of an fp32 NCHW batch (n, c, ih, iw) -> (n, c, oh, ow), the per-step rescale
+ * of `train.py --multi-scale` (reference train.py:368-374: F.interpolate(imgs, size=ns, mode='bilinear', align_corners=False)).
+ * Per axis, for output index d, input size `in` and scale = (float)in / (float)out computed by the CALLER in fp32:
+ *   s  = max(scale * (d + 0.5f) - 0.5f, 0);  i0 = min((int)s, in - 1);  i1 = min(i0 + 1, in - 1);  l1 = s - (float)i0;  l0 = 1 - l1
+ *   dst = hy0 * (wx0 * a + wx1 * b) + hy1 * (wx0 * c + wx1 * d),  a, b = src[y0][x0], src[y0][x1];  c, d = src[y1][x0], src[y1][x1]
+ * Every product and sum is rounded to fp32 once (no FMA contraction), so the result is a function of the formula alone: it differs
+ * from ATen's GPU kernel (which may contract) by rounding only, never by more than ATen's own fp32 result differs from a float64
+ * evaluation (tests/test_multiscale.py).  Equal sizes return the input bits (finite inputs).  Any n, c and sizes >= 1; src and dst
+ * are dense, 4-byte aligned and may not overlap.  One wave per 64-pixel segment of an output row, no LDS, no atomics, no workspace.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed.                                                     */
+typedef struct yh_resize_desc {
+    const float* src;            /* [n][c][ih][iw]                                                                   */
+    float* dst;                  /* [n][c][oh][ow]                                                                   */
+    int32_t n, c, ih, iw, oh, ow;
+    float scale_h, scale_w;      /* (float)ih / (float)oh, (float)iw / (float)ow                                     */
+} yh_resize_desc;
+int yh_resize_bilinear(const yh_resize_desc* d, void* stream);
+
 /* Input pipeline on the device, second slice: ONE training item = 4-image mosaic -> random affine warp (bilinear, constant
  * border) -> HSV augmentation -> left-right flip -> planar CHW uint8 or x / divisor float.  Replaces utils/datasets.py
  * load_mosaic + random_affine + augment_hsv + the flip / transpose of __getitem__ (reference datasets.py:553-608, 649-715, 534-550,

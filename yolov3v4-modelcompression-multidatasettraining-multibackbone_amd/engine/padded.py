@@ -328,8 +328,19 @@ class PaddedTrainEngine:
     _current = property(lambda self: self.inner._current)
     lib = property(lambda self: self.inner.lib)
 
+    _arena = property(lambda self: self.inner._arena)
+
     def _get_plan(self, x):
         return self.inner._get_plan(x)
+
+    def reserve(self, shapes):
+        self.inner.reserve(shapes)      # the twin reads the model's input channels: the shapes carry over
+
+    def train_stats(self):
+        return self.inner.train_stats()
+
+    def _drop_plans(self):
+        self.inner._drop_plans()
 
     def set_bn_sparsity(self, block_indices, s):
         """The twin has the model's blocks one for one, so the set carries over.  The term s * sign(gamma) is added in the TWIN's
@@ -365,13 +376,15 @@ class PaddedTrainEngine:
 
 
 def make_train_engine(model, precision, x, lib=None):
-    """The training engine for ``model`` and input batch ``x``: the aligned lowering when every width is a multiple of 8, the
-    padded twin otherwise.  Plan build errors (NotImplementedError) surface here, before any state changes."""
+    """The training engine for ``model`` and input batch ``x`` (or its (N, C, H, W) shape, when no batch exists yet): the aligned
+    lowering when every width is a multiple of 8, the padded twin otherwise.  Plan build errors (NotImplementedError) surface here,
+    before any state changes."""
     from .train import TrainEngine, ChannelAlignmentError
+    first_plan = (lambda eng: eng._get_plan(x)) if torch.is_tensor(x) else (lambda eng: eng.reserve([x]))
     try:
         eng = TrainEngine(model, precision, lib)
-        eng._get_plan(x)
+        first_plan(eng)
     except ChannelAlignmentError:
         eng = PaddedTrainEngine(model, precision, lib)
-        eng._get_plan(x)
+        first_plan(eng)
     return eng

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import hiplib, imgtables
-from .hiplib import LetterboxDesc
+from .hiplib import LetterboxDesc, ResizeDesc
 
 PRECISION_BITS = 32 - 8 - 2      # Pillow: 8-bit samples, 22 fractional coefficient bits
 PAD_VALUE = 114
@@ -210,6 +210,29 @@ def resize_to_device(frame, out_hw, device, code=imgtables.ARITH_CV2_LINEAR, lib
             keep = [torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in (hb, hk, vb, vk)]
             d.hbounds, d.hk, d.vbounds, d.vk = (P(t) for t in keep)
         hiplib.check(lib.yh_letterbox_fwd(C.byref(d), hiplib.stream_ptr()), 'yh_letterbox_fwd')
+    return out
+
+
+def resize_bilinear(x, size, out=None, lib=None):
+    """Bilinear resize of an fp32 NCHW batch to ``size`` = (oh, ow) on the device (``yh_resize_bilinear``, csrc/resize.hip): the
+    arithmetic of ``F.interpolate(x, size=size, mode='bilinear', align_corners=False)``, every operation rounded to fp32 once - what
+    ``train.py --multi-scale`` rescales each batch with on the HIP path."""
+    lib = lib or hiplib.load()
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError('expected an fp32 (N, C, H, W) batch')
+    x = x.contiguous()
+    n, c, ih, iw = x.shape
+    oh, ow = int(size[0]), int(size[1])
+    if min(n, c, ih, iw, oh, ow) < 1:
+        raise ValueError('resize_bilinear: empty batch or size')
+    if out is None:
+        out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, c, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('resize_bilinear: out must be a contiguous fp32 (N, C, oh, ow) tensor on the input device')
+    d = ResizeDesc(src=hiplib.ptr(x), dst=hiplib.ptr(out), n=n, c=c, ih=ih, iw=iw, oh=oh, ow=ow,
+                   scale_h=float(np.float32(ih) / np.float32(oh)), scale_w=float(np.float32(iw) / np.float32(ow)))
+    with hiplib.on_device(x):
+        hiplib.check(lib.yh_resize_bilinear(C.byref(d), hiplib.stream_ptr()), 'yh_resize_bilinear')
     return out
 
 

@@ -24,6 +24,9 @@ and the backward plan, walking the values in reverse,
     grad(input) (+)= conv(dz, W^T flipped)     yh_conv2d_fwd on the dgrad weight image (stride 2: four parity phases)
 
 Every activation, z and gradient buffer is kept for the whole step (288 GB of HBM: YOLOv3-608 batch 64 needs ~40 GB).
+They are pieces of ONE byte arena per engine that the plans of all input shapes share (``_StepArena``; multi-scale training draws
+a new shape every step): a plan records offsets and binds the arena through a plan slot, so it may not assume that a buffer still
+holds what its build or its previous step left there.  ``reserve`` sizes the arena ahead of the first step.
 Depthwise blocks, squeeze-excite, max-pools (incl. SPP) and CSP group-split routes are lowered too (csrc/depthwise.hip,
 csrc/train.hip).  Graphs whose widths are not multiples of 8 (slim-pruned nets, GhostNet) train through the channel-padded twin
 of ``engine/padded.py``; what neither form covers (weighted shortcuts, grouped convs other than depthwise) raises
@@ -71,8 +74,8 @@ class _Arena:
         self.size += _round_up(n, 4)
         return off
 
-    def allocate(self, device):
-        self.buf = torch.zeros(max(self.size, 4), device=device, dtype=torch.float32)
+    def allocate(self, state):
+        self.buf = state.tensor(max(self.size, 4), torch.float32, zero=True)
         return self.buf
 
     def ptr(self, off):
@@ -82,12 +85,100 @@ class _Arena:
         return self.buf[off:off + n]
 
 
+SLOT_ARENA = 62      # base of the engine's step arena: every activation / gradient / scratch pointer of a plan is a fixup on it
+ARENA_ALIGN = 512    # what torch's allocator gave these buffers when each was a tensor of its own
+# While a plan is being built its step buffers have no address yet: a pointer into piece k reads TAG | k << 40 | byte offset.  Bit 62
+# makes it a non-canonical address no allocator returns, so a descriptor field holding one is recognised by value; equal buffers
+# still compare equal and keep their alignment, which is all the library's geometry queries look at.
+_PIECE_TAG, _PIECE_SHIFT = 1 << 62, 40
+
+
+class _Piece:
+    """A step buffer of one plan: a byte range of the engine's step arena, placed when the plan is complete."""
+    __slots__ = ('arena', 'index', 'n', 'dtype', 'off')
+
+    def __init__(self, arena, index, n, dtype):
+        self.arena, self.index, self.n, self.dtype, self.off = arena, index, int(n), dtype, None
+
+    def numel(self):
+        return self.n
+
+    def element_size(self):
+        return torch.empty(0, dtype=self.dtype).element_size()
+
+    def nbytes(self):
+        return self.n * self.element_size()
+
+    def data_ptr(self):
+        return _PIECE_TAG | (self.index << _PIECE_SHIFT)
+
+    def zero_(self):
+        self.arena.view(self.off, self.n, self.dtype).zero_()
+
+
+class _StepArena:
+    """The byte arena all plans of a training engine carve their step buffers from.  Only one plan's step is alive at a time, so
+    plans alias each other; it only grows, to the largest requirement met (or reserved) so far."""
+
+    def __init__(self):
+        self.buf, self.base, self.capacity, self.allocs = None, 0, 0, 0
+
+    def ensure(self, nbytes, device):
+        """True when a new arena had to be allocated (every plan must then re-bind, and a step in flight is lost)."""
+        if nbytes <= self.capacity and self.buf is not None:
+            return False
+        self.buf = None                       # release first: the old and the new arena never coexist
+        self.buf = torch.empty(nbytes + ARENA_ALIGN, device=device, dtype=torch.uint8)
+        self.base = _round_up(self.buf.data_ptr(), ARENA_ALIGN)
+        self.capacity = nbytes
+        self.allocs += 1
+        return True
+
+    def release(self):
+        self.buf, self.base, self.capacity = None, 0, 0
+
+    def view(self, off, n, dtype):
+        first = self.base - self.buf.data_ptr() + off
+        return self.buf[first:first + n * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+
+class _PlanState:
+    """The state a plan keeps outside the arena (weight images, statistics / gradient arenas, tables), carved at 512-byte alignment
+    from a few chunks of at least 4 MiB instead of one device allocation per tensor: a plan build then leaves a handful of large
+    blocks in torch's allocator, not some hundred small ones scattered among the step's transient tensors, where they would pin
+    fragments that later steps can no longer reuse."""
+    CHUNK = 4 << 20
+
+    def __init__(self, device):
+        self.device, self.chunks, self.left, self.used = device, [], 0, 0
+
+    def tensor(self, n, dtype, zero=False):
+        nbytes = max(int(n), 1) * torch.empty(0, dtype=dtype).element_size()
+        room = _round_up(nbytes, ARENA_ALIGN)
+        if room > self.left:
+            size = max(room, min(self.CHUNK << len(self.chunks), 64 << 20))
+            chunk = torch.empty(size + ARENA_ALIGN, device=self.device, dtype=torch.uint8)
+            self.chunks.append(chunk)
+            self.pos = _round_up(chunk.data_ptr(), ARENA_ALIGN) - chunk.data_ptr()
+            self.left = size
+        t = self.chunks[-1][self.pos:self.pos + nbytes].view(dtype)[:int(n)]
+        self.pos += room
+        self.left -= room
+        self.used += room
+        return t.zero_() if zero else t
+
+
 class TrainEngine(DarknetEngine):
     def __init__(self, model, precision='fp16', lib=None):
         if precision not in ('fp16', 'fp32'):
             raise ValueError("training precision must be 'fp16' or 'fp32'")
         super().__init__(model, precision, lib)
         self._tplans = {}
+        # plans own descriptors and small per-shape state only (the step buffers live in the arena), so many stay resident:
+        # 17 multi-scale sizes plus the shorter last batch of an epoch at each
+        self.max_train_plans = max(1, int(os.environ.get('YOLO_HIP_MAX_TRAIN_PLANS', '40')))
+        self._arena = _StepArena()
+        self.plan_builds = 0
         self._current = None
         self.steps = 0   # forward count; the autograd node checks it so a stale backward fails loudly
         self._l1_blocks = ()   # network-slimming sparsity: blocks whose BatchNorm gamma carries the L1 penalty (set_bn_sparsity)
@@ -224,7 +315,7 @@ class TrainEngine(DarknetEngine):
         if table is None or table.numel() < host.numel():
             # sized for every BatchNorm of the graph, so a later change of the set rewrites it in place
             cap = sum(1 for v in plan['values'] if v.kind in ('conv', 'dw') and getattr(v, 'bn', None) is not None)
-            table = plan['l1_table'] = torch.zeros(max(cap, len(items)) * C.sizeof(BnL1Row), device=self.device, dtype=torch.uint8)
+            table = plan['l1_table'] = plan['state'].tensor(max(cap, len(items)) * C.sizeof(BnL1Row), torch.uint8, zero=True)
         table[:host.numel()].copy_(host)
         ranges, r = [], 0
         for k in range(len(plan['segments'])):
@@ -259,7 +350,8 @@ class TrainEngine(DarknetEngine):
         self._check_supported(values)
         self._place(values)
         lib, dev, P = self.lib, self.device, hiplib.ptr
-        plan = dict(values=values, heads=heads, N=N, storages=[], fwd_ops=[], bwd_ops=[], zero_list=[], ws_floats=0, ws2_floats=0)
+        plan = dict(values=values, heads=heads, N=N, storages=[], fwd_ops=[], bwd_ops=[], zero_list=[], ws_floats=0, ws2_floats=0,
+                    arena=self._arena, arena_refs=[], state=_PlanState(dev), bound=None)
         fwd = plan['fwd'] = lib.yh_plan_create()
         bwd = plan['bwd'] = lib.yh_plan_create()
         if not fwd or not bwd:
@@ -273,6 +365,11 @@ class TrainEngine(DarknetEngine):
             if idx < 0:
                 hiplib.check(idx, 'yh_plan_add(%s)' % what)
             log.append((what, desc))
+            for name, ctype in desc._fields_:
+                val = getattr(desc, name) if ctype is C.c_void_p else None
+                if val and val >> 62 == 1:          # a step buffer: becomes a fixup on the arena slot once the pieces are placed
+                    plan['arena_refs'].append((handle, idx, getattr(type(desc), name).offset, (val ^ _PIECE_TAG) >> _PIECE_SHIFT,
+                                               val & ((1 << _PIECE_SHIFT) - 1), what))
             return idx
 
         def fixup(handle, op, desc_type, field, slot):
@@ -292,10 +389,22 @@ class TrainEngine(DarknetEngine):
                 fixup(handle, op, type(desc), 'ws', SLOT_WS2 if side else SLOT_WS)
             return op
 
-        def alloc(shape, fp32=False, zero=False):
-            t = (torch.zeros if zero else torch.empty)(shape, device=dev, dtype=torch.float32 if fp32 else self.dtype)
+        pieces = []
+
+        def alloc(shape, fp32=False):
+            """A step buffer: a piece of the engine's arena, which other plans overwrite between two steps of this one - nothing
+            may rely on what an earlier step (or the build) left in it."""
+            n = 1
+            for k in shape:
+                n *= int(k)
+            t = _Piece(self._arena, len(pieces), n, torch.float32 if fp32 else self.dtype)
+            pieces.append(t)
             plan['storages'].append(t)
             return t
+
+        def keep(n, dtype, zero=False):
+            """State the plan keeps for itself, outside the arena (counted in plan_bytes)."""
+            return plan['state'].tensor(n, dtype, zero)
 
         def materialize(v):
             if v.storage is not None:
@@ -336,8 +445,8 @@ class TrainEngine(DarknetEngine):
                     plan['param_slices'].append((v.g_beta, v.C, (v.C,)))
                     v.s_sum, v.s_sumsq = stats.reserve(v.C), stats.reserve(v.C)
                     v.s_mean, v.s_invstd = saved.reserve(v.C), saved.reserve(v.C)
-                v.tpack = dict(w=torch.empty(v.k * v.k * v.c_phys, device=dev, dtype=self.dtype),
-                               b=torch.empty(v.c_phys, device=dev, dtype=torch.float32))
+                v.tpack = dict(w=keep(v.k * v.k * v.c_phys, self.dtype),
+                               b=keep(v.c_phys, torch.float32))
                 v.plain = bn is None and v.act == LINEAR
                 v.z = None if v.plain else alloc((N, v.H, v.W, v.c_phys))
                 v.res, v.ups, v.Ho, v.Wo, v.fp32 = None, 1, v.H, v.W, False
@@ -375,30 +484,30 @@ class TrainEngine(DarknetEngine):
                 v.s_mean, v.s_invstd = saved.reserve(v.C), saved.reserve(v.C)
             if v.src.kind == 'input':
                 cout_pad = _round_up(v.C, 32) if v.C % 32 == 0 else _round_up(v.C, 16)
-                v.tpack = dict(w=torch.empty(taps * v.src.C * cout_pad, device=dev, dtype=torch.float32),
-                               b=torch.empty(cout_pad, device=dev, dtype=torch.float32), cout_pad=cout_pad)
+                v.tpack = dict(w=keep(taps * v.src.C * cout_pad, torch.float32),
+                               b=keep(cout_pad, torch.float32), cout_pad=cout_pad)
             else:
                 cin_k = _round_up(v.src.c_phys, kstep)
                 m_pad = _round_up(v.c_phys, 128)
                 cout_k = _round_up(v.c_phys, kstep)          # dgrad: K runs over the output channels
                 dm_pad = _round_up(v.src.c_phys, 128)
-                v.tpack = dict(w=torch.empty(m_pad * taps * cin_k, device=dev, dtype=self.dtype),
-                               b=torch.empty(m_pad, device=dev, dtype=torch.float32), cin_k=cin_k, m_pad=m_pad,
-                               wt=None if v.stride == 2 else torch.empty(dm_pad * taps * cout_k, device=dev, dtype=self.dtype),
+                v.tpack = dict(w=keep(m_pad * taps * cin_k, self.dtype),
+                               b=keep(m_pad, torch.float32), cin_k=cin_k, m_pad=m_pad,
+                               wt=None if v.stride == 2 else keep(dm_pad * taps * cout_k, self.dtype),
                                cout_k=cout_k, dm_pad=dm_pad)
                 if self._dgrad_fused_into_stem(values, v):
                     v.tpack['stem_fused'] = True
-                    v.tpack['wt'] = torch.empty(dm_pad * taps * cout_k, device=dev, dtype=self.dtype)
+                    v.tpack['wt'] = keep(dm_pad * taps * cout_k, self.dtype)
                 elif v.stride == 2 and 16 <= v.src.c_phys <= _FUSED_DGRAD_MAX_CIN and v.src.c_phys % 4 == 0:
                     # few input channels: the data gradient is bound by reading dz and writing dx, so all four parity phases
                     # run as ONE 2x2-tap GEMM with 4 * cin rows (16 tap-GEMMs instead of 9, but dz is read once, not four
                     # times, and each workgroup writes whole rows of dx): yh_conv2d_fwd ups = 4
                     v.tpack['fused_m_pad'] = _round_up(4 * v.src.c_phys, 128)
-                    v.tpack['wt_fused'] = torch.empty(v.tpack['fused_m_pad'] * 4 * cout_k, device=dev, dtype=self.dtype)
+                    v.tpack['wt_fused'] = keep(v.tpack['fused_m_pad'] * 4 * cout_k, self.dtype)
                 elif v.stride == 2:
                     # parity (a, b) sees ((a + pad) // 2 + 1) x ((b + pad) // 2 + 1) taps
                     v.tpack['phase_taps'] = [((a + v.pad) // 2 + 1, (b + v.pad) // 2 + 1) for a in (0, 1) for b in (0, 1)]
-                    v.tpack['wt_phase'] = [torch.empty(dm_pad * th * tw * cout_k, device=dev, dtype=self.dtype)
+                    v.tpack['wt_phase'] = [keep(dm_pad * th * tw * cout_k, self.dtype)
                                            for th, tw in v.tpack['phase_taps']]
             # z: the conv output before BN / activation.  Blocks with neither BN nor activation store straight to y.
             v.plain = bn is None and v.act == LINEAR and v.res is None and v.ups == 1
@@ -412,14 +521,16 @@ class TrainEngine(DarknetEngine):
                 v.z = alloc((N, v.Ho, v.Wo, v.c_phys))
         plan['junk_n'] = max(v.c_phys for v in values if v.kind in ('conv', 'dw'))
         plan['junk'] = grads.reserve(plan['junk_n'])
-        stats.allocate(dev)
-        saved.allocate(dev)
-        grads.allocate(dev)
+        stats.allocate(plan['state'])
+        saved.allocate(plan['state'])
+        grads.allocate(plan['state'])
         # one zero row serves every data gradient as its bias: as long as the longest m_pad among them, incl. the one-pass stride-2 form's
         # 4 * cin rows (a narrow / pruned net whose widest conv input is <= 128 but that has a stride-2 conv with 33 .. 64
         # inputs needs 256 there and failed at plan build)
-        zero_bias = alloc((max([max(_round_up(v.src.c_phys, 128), v.tpack.get('fused_m_pad', 0))
-                                for v in values if v.kind == 'conv' and v.src.kind != 'input'] + [128]),), fp32=True, zero=True)
+        # (it is read-only and its length does not depend on the input shape: the plan's own, outside the arena, so no step has to
+        # zero it again after another plan used the arena)
+        zero_bias = keep(max([max(_round_up(v.src.c_phys, 128), v.tpack.get('fused_m_pad', 0))
+                              for v in values if v.kind == 'conv' and v.src.kind != 'input'] + [128]), torch.float32, zero=True)
         dz_elems = max(N * v.Ho * v.Wo * v.c_phys for v in values if v.kind in ('conv', 'dw'))
         # Two lanes in the backward plan (include/yolo_hip.h yh_plan_set_lane), OFF by default: the weight gradient of a layer only
         # feeds the optimizer, so it can run on the plan's side stream, issued after the layer's data gradient, while the main chain
@@ -463,8 +574,7 @@ class TrainEngine(DarknetEngine):
         head_index = {id(h.src): k for k, h in enumerate(heads)}
 
         raw, n_items = self._pack_items(plan)
-        plan['pack_table'] = torch.zeros(len(raw), device=dev, dtype=torch.uint8)
-        plan['storages'].append(plan['pack_table'])
+        plan['pack_table'] = keep(len(raw), torch.uint8, zero=True)
         add(fwd, plan['fwd_ops'], PackBatchDesc(items=plan['pack_table'].data_ptr(), n_items=n_items), 'pack')
 
         # ---- pass 2: forward ops
@@ -900,10 +1010,33 @@ class TrainEngine(DarknetEngine):
         plan['ws2'] = alloc((max(plan['ws2_floats'], 4),), fp32=True)
         if async_reduce:
             hiplib.check(lib.yh_plan_set_async_reduce(bwd, 1), 'yh_plan_set_async_reduce')
-        for handle in (fwd, bwd):
-            lib.yh_plan_bind_slot(handle, SLOT_WS, plan['ws'].data_ptr())
-        lib.yh_plan_bind_slot(bwd, SLOT_WS2, plan['ws2'].data_ptr())
+        # place the pieces that are still in use (the residual-gradient aliasing above dropped some) and turn every pointer into
+        # them into a fixup on the arena slot: the plan holds offsets, `_bind` gives it the arena's address
+        need = 0
+        for t in plan['storages']:
+            t.off = need
+            need += _round_up(t.nbytes(), ARENA_ALIGN)
+        plan['arena_need'] = need
+        for handle, op, field, index, inner, what in plan['arena_refs']:
+            t = pieces[index]
+            if t.off is None or inner >= max(t.nbytes(), 1):
+                raise RuntimeError('%s points into a step buffer the plan does not keep' % what)
+            hiplib.check(lib.yh_plan_add_fixup(handle, op, field, SLOT_ARENA, t.off + inner), 'fixup')
+        del plan['arena_refs']
+        # what stays per plan: statistics, saved, gradient arenas, pack table, zero bias row and the weight images
         return plan
+
+    def _bind(self, plan):
+        """Give the plan the arena's current address (after its build, and again after the arena grew)."""
+        base = self._arena.base
+        if plan['bound'] == base:
+            return
+        lib = self.lib
+        for handle in (plan['fwd'], plan['bwd']):
+            lib.yh_plan_bind_slot(handle, SLOT_ARENA, base)
+            lib.yh_plan_bind_slot(handle, SLOT_WS, base + plan['ws'].off)
+        lib.yh_plan_bind_slot(plan['bwd'], SLOT_WS2, base + plan['ws2'].off)
+        plan['bound'] = base
 
     def _stem_bwd_fused(self, v, s):
         """The one-pass backward of the first block applies: fp16 step, 3x3 / stride 1 / pad 1 on a 1- or 3-channel image, 16 or
@@ -951,21 +1084,54 @@ class TrainEngine(DarknetEngine):
             self.device = x.device
         elif self.device != x.device:
             raise RuntimeError('engine was built on %s, input is on %s' % (self.device, x.device))
-        key = tuple(x.shape)
+        return self._plan_for(tuple(x.shape))
+
+    def _cached_plan(self, key):
+        """The plan of input shape ``key``, built on first use.  Plans hold descriptors and small per-shape state; the step buffers
+        of all of them alias in the engine's arena, so the least recently used ones are evicted by count only (their native handles
+        go, the arena is not touched)."""
         plan = self._tplans.get(key)
         if plan is None:
-            # a plan owns every activation and gradient buffer of a step: keep only the two most recent input shapes
-            # (multi-scale training walks through a dozen sizes)
-            while len(self._tplans) >= 2:
+            while len(self._tplans) >= self.max_train_plans:
                 old = self._tplans.pop(next(iter(self._tplans)))
                 for h in ('fwd', 'bwd'):
                     self.lib.yh_plan_destroy(old[h])
                 if self._current is old:
                     self._current = None
-            plan = self._tplans[key] = self._build_train_plan(*key)
+            plan = self._build_train_plan(*key)
+            self.plan_builds += 1
+            self._tplans[key] = plan
         else:
             self._tplans[key] = self._tplans.pop(key)   # most recently used last
         return plan
+
+    def _ensure_arena(self, nbytes):
+        if self._arena.ensure(nbytes, self.device):
+            # a new arena: the activations of a forward still waiting for its backward went with the old one
+            self._current = None
+            self.steps += 1
+
+    def _plan_for(self, key):
+        plan = self._cached_plan(key)
+        self._ensure_arena(plan['arena_need'])
+        return plan
+
+    def reserve(self, shapes):
+        """Size the arena for the input shapes ``shapes`` [(N, C, H, W)] without running a step: their plans are built (and stay
+        in the cache), the arena is allocated once for the largest.  Fails here, not at the first step of that shape, when the
+        device cannot hold it."""
+        shapes = [tuple(int(k) for k in shape) for shape in shapes]
+        if any(len(shape) != 4 for shape in shapes):
+            raise ValueError('reserve() takes (N, C, H, W) shapes')
+        if self.device is None:
+            self.device = next(self.model.parameters()).device
+        self._ensure_arena(max([self._cached_plan(key)['arena_need'] for key in shapes] + [self._arena.capacity]))
+
+    def train_stats(self):
+        plans = list(self._tplans.values())
+        return dict(plan_builds=self.plan_builds, arena_allocs=self._arena.allocs, arena_bytes=self._arena.capacity,
+                    plans_resident=len(plans),
+                    plan_bytes=sum(p['state'].used for p in plans))
 
     def forward(self, x):
         """Run the training forward; returns the fp32 NHWC head tensors [(N, ny, nx, c_phys)] (fresh tensors)."""
@@ -973,6 +1139,7 @@ class TrainEngine(DarknetEngine):
         if x.dtype != torch.float32:
             x = x.float()
         plan = self._get_plan(x)
+        self._bind(plan)
         self._refresh_pack_table(plan)   # the packing itself is op 0 of the forward plan (one launch)
         self._refresh_l1_table(plan)
         lib = self.lib
@@ -986,6 +1153,8 @@ class TrainEngine(DarknetEngine):
                     if v.kind == 'conv' and v.bn is not None and v.bn.num_batches_tracked is not None]
         if counters:
             torch._foreach_add_(counters, 1)
+        if self._current is not None:      # many plans stay resident: only the plan of the step in flight keeps its input and head gradients
+            self._current['x'], self._current['bwd_keep'] = None, []
         plan['x'] = x
         self._current = plan
         self.steps += 1
@@ -1087,3 +1256,6 @@ class TrainEngine(DarknetEngine):
                 except Exception:
                     pass
         self._tplans = {}
+        self._current = None
+        if getattr(self, '_arena', None) is not None:
+            self._arena.release()

@@ -488,6 +488,33 @@ class Darknet(nn.Module):
         if eng is not None:
             eng.set_bn_sparsity(*self.__dict__['_hip_bn_sparsity'])
 
+    def hip_reserve_train(self, shapes, precision=None):
+        """Multi-scale training: size the HIP training engine's step arena for every input shape of ``shapes`` (an iterable of
+        ``(N, C, H, W)``) before the first step.  All shapes of a run share that one arena (engine/train.py), so after a reservation
+        that covers the largest of them no step allocates device memory again, and a run that does not fit fails here.  No step is
+        run; graphs that train through the channel-padded twin reserve through it.  ``precision``: as the steps will run
+        (``'fp16'`` under autocast, ``'fp32'`` otherwise; ``YOLO_HIP_TRAIN_PRECISION`` overrides)."""
+        from engine.padded import make_train_engine  # raises if libyolo_hip.so is missing: no fallback
+        shapes = [tuple(int(k) for k in shape) for shape in shapes]
+        if not shapes:
+            return
+        precision = os.environ.get('YOLO_HIP_TRAIN_PRECISION') or precision or ('fp16' if torch.is_autocast_enabled() else 'fp32')
+        eng = self.__dict__.get('_hip_train_engine')
+        with _on_device(next(self.parameters()).device):
+            if eng is None or eng.precision != precision:
+                eng = make_train_engine(self, precision, max(shapes, key=lambda s: s[0] * s[2] * s[3]))
+                self.__dict__['_hip_train_engine'] = eng
+            eng.reserve(shapes)
+
+    def hip_train_stats(self):
+        """Counters of the HIP training engine: ``plan_builds`` (plans built so far), ``arena_allocs`` (device allocations of the
+        step arena), ``arena_bytes`` (its capacity), ``plans_resident`` and ``plan_bytes`` (the per-plan state outside the arena:
+        weight images, statistics and gradient arenas, tables - summed over the resident plans)."""
+        eng = self.__dict__.get('_hip_train_engine')
+        if eng is None:
+            return dict(plan_builds=0, arena_allocs=0, arena_bytes=0, plans_resident=0, plan_bytes=0)
+        return eng.train_stats()
+
     def _forward_hip(self, x):
         from engine.plan import DarknetEngine  # raises if libyolo_hip.so is missing: no fallback
         eng = self.__dict__.get('_hip_engine')

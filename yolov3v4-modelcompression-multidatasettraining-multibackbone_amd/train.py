@@ -101,6 +101,11 @@ def sparsity_layers(prune, module_defs):
     return sparsity_blocks(module_defs, prune)
 
 
+def hip_train_path(device, opt):
+    """The training step of this run goes through the HIP engine (models.Darknet._use_hip_train): GPU tensors, float graph."""
+    return device.type == 'cuda' and opt.quantized == -1
+
+
 def train(opt, hyp):
     cfg, data, epochs, batch_size, weights = opt.cfg, opt.data, opt.epochs, opt.batch_size, opt.weights
     imgsz_min, imgsz_max, imgsz_test = opt.img_size
@@ -219,6 +224,14 @@ def train(opt, hyp):
         if sparsity_in_step:
             core.hip_set_bn_sparsity(prune_idx, opt.s)
 
+    hip_step = hip_train_path(device, opt)
+    if opt.multi_scale and hip_step:
+        # every size of the run shares one step arena (engine/train.py): sized here for the largest, so no step allocates device memory
+        # again and a run that does not fit fails now, not at the first draw of the largest size
+        core.hip_reserve_train([(batch_size, 1 if opt.gray_scale else 3, imgsz_max, imgsz_max)], precision='fp16' if opt.mpt else 'fp32')
+        if _is_main(rank):
+            print('HIP step arena: %d bytes for every image size up to %g' % (core.hip_train_stats()['arena_bytes'], imgsz_max))
+
     nb = len(dataloader)
     n_burn = max(3 * nb, 500)
     maps = np.zeros(nc)
@@ -271,7 +284,11 @@ def train(opt, hyp):
                 sf = img_size / max(imgs.shape[2:])
                 if sf != 1:
                     ns = [math.ceil(x * sf / gs) * gs for x in imgs.shape[2:]]
-                    imgs = torch.nn.functional.interpolate(imgs, size=ns, mode='bilinear', align_corners=False)
+                    if hip_step and imgs.is_cuda:     # the same formula on our own kernel, pinned rounding (csrc/resize.hip)
+                        from engine.preprocess import resize_bilinear
+                        imgs = resize_bilinear(imgs, ns)
+                    else:
+                        imgs = torch.nn.functional.interpolate(imgs, size=ns, mode='bilinear', align_corners=False)
 
             with torch.autocast(device.type if device.type != 'cpu' else 'cpu', dtype=torch.float16,
                                 enabled=opt.mpt and device.type != 'cpu'):

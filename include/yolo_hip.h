@@ -532,6 +532,59 @@ typedef struct yh_bn_l1_row {
 } yh_bn_l1_row;
 int yh_bn_l1_subgrad(const yh_bn_l1_row* rows, int first, int last, float s, void* stream);
 
+/* Evaluation statistics of one batch (csrc/evalmatch.hip): which detections are true positives - the per-image loop of the mAP
+ * protocol (reference test.py:139-185: clip_coords, per label class two nonzero calls, a box_iou and one host read per
+ * over-threshold detection) as ONE launch, one workgroup of 256 threads per image.  For image b with detections pred (n, 6)
+ * [x1, y1, x2, y2, conf, cls] and its labels (cls, normalised xywh) in the order label_index lists them:
+ *   1. clip: x1 / x2 to [0, width], y1 / y2 to [0, height], written back IN PLACE (torch.clamp_: a NaN stays a NaN);
+ *   2. label boxes: x1 = (x - w / 2) * width, y1 = (y - h / 2) * height, x2 = (x + w / 2) * width, y2 = (y + h / 2) * height;
+ *   3. per detection the same-class label (float equality) of the largest IoU, the LOWEST label index on a tie; IoU =
+ *      inter / ((a1 + a2) - inter), a = (x2 - x1) * (y2 - y1), inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0); a
+ *      detection claims that label when the IoU > iouv[0] (strict; a NaN IoU among its same-class labels: no claim);
+ *   4. a label is won by its LOWEST-index claimant (an integer minimum on a claim slot in LDS: order-independent, the result
+ *      is the same bits from run to run); correct[p][k] = IoU_p > iouv[k] for winners, 0 for every other row.
+ * Every operation is a single fp32 operation in this order (no contraction, IEEE divide): the flags are those of the host
+ * loop bit for bit.  conf_cls receives a packed copy of columns 4 and 5, so that one read of `correct` and `conf_cls` is all
+ * the host needs.  No float atomics.
+ *   rows         DEVICE table, one row per image, 8-byte aligned.  pred NULL or n == 0: the image has no detections (its
+ *                workgroup returns at once).  Rows of different images may point into different buffers.
+ *   targets      DEVICE (nt, 6) fp32 [image, cls, x, y, w, h] as the loader made them, in any order
+ *   label_index  DEVICE nt int32: row numbers of `targets` grouped by image (stable within an image); image b's labels are
+ *                label_index[lab_first .. lab_first + nl).  The binding builds it from the loader's host copy.
+ *   iouv         DEVICE niou fp32 thresholds, 1 <= niou <= 10
+ *   correct      DEVICE uint8 (total, niou); conf_cls DEVICE fp32 (total, 2), 4-byte aligned; image b's rows start at out_off
+ *   ws           DEVICE workspace, 4-byte aligned, ws_bytes >= 8 * total + 4 * nt: per detection its best label and IoU
+ *                between the two phases, and the claim slots of images whose labels do not fit the LDS staging
+ * Any n and any nl: up to YH_EVAL_MATCH_LDS_LABELS labels of an image are staged in LDS (box, class) with their claim slots;
+ * an image with more walks its labels in chunks of that size and keeps its claim slots in `ws` - slower, same result.
+ * Null or misaligned arguments, niou outside [1, 10], negative counts, a workspace that is too small: YH_EINVAL / YH_EALIGN
+ * before any launch.  images == 0 or total == 0: YH_OK, nothing is launched.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed. */
+#define YH_EVAL_MATCH_LDS_LABELS 512
+typedef struct yh_eval_match_row {
+    float* pred;            /* (n, 6) fp32, dense rows, 4-byte aligned; clipped in place                         */
+    int32_t n;              /* detections of the image                                                          */
+    int32_t out_off;        /* its first row in correct / conf_cls                                              */
+    int32_t lab_first;      /* its first entry in label_index                                                   */
+    int32_t nl;             /* its labels                                                                       */
+} yh_eval_match_row;
+typedef struct yh_eval_match_desc {
+    const yh_eval_match_row* rows;
+    const float* targets;
+    const int32_t* label_index;
+    const float* iouv;
+    uint8_t* correct;
+    float* conf_cls;
+    void* ws;
+    int64_t ws_bytes;
+    int32_t images;         /* rows of the table = workgroups                                                   */
+    int32_t nt;             /* rows of targets = entries of label_index                                         */
+    int32_t total;          /* rows of correct / conf_cls: the sum of n                                         */
+    int32_t niou;
+    float width, height;    /* the network input, in pixels                                                     */
+} yh_eval_match_desc;
+int yh_eval_match(const yh_eval_match_desc* d, void* stream);
+
 typedef struct yh_wgrad_desc {
     const void* x;          /* forward input of the conv, NHWC dtype (stem: NCHW fp32 image)                    */
     const void* dz;         /* gradient of the conv output, NHWC dtype, pitch lddz                              */

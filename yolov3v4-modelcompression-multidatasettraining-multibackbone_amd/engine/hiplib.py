@@ -200,6 +200,18 @@ class BnL1Row(C.Structure):
     _fields_ = [('gamma', _vp), ('grad', _vp), ('n', _i32), ('reserved', _i32)]
 
 
+class EvalMatchRow(C.Structure):
+    _fields_ = [('pred', _vp), ('n', _i32), ('out_off', _i32), ('lab_first', _i32), ('nl', _i32)]
+
+
+class EvalMatchDesc(C.Structure):
+    _fields_ = [('rows', _vp), ('targets', _vp), ('label_index', _vp), ('iouv', _vp), ('correct', _vp), ('conf_cls', _vp), ('ws', _vp),
+                ('ws_bytes', _i64), ('images', _i32), ('nt', _i32), ('total', _i32), ('niou', _i32), ('width', _f32), ('height', _f32)]
+
+
+EVAL_MATCH_LDS_LABELS = 512     # YH_EVAL_MATCH_LDS_LABELS: labels of one image the kernel stages in LDS (more: its chunked form)
+
+
 class DwBwdDesc(C.Structure):
     _fields_ = [('x', _vp), ('dz', _vp), ('w', _vp), ('dx', _vp), ('dw', _vp),
                 ('n', _i32), ('h', _i32), ('w_in', _i32), ('c', _i32), ('ho', _i32), ('wo', _i32), ('k', _i32), ('stride', _i32),
@@ -302,6 +314,7 @@ _SIGNATURES = {
     'yh_maxpool2d_bwd': (C.c_int, [C.POINTER(PoolBwdDesc), _vp]),
     'yh_pack_batch': (C.c_int, [_vp, C.c_int, _vp]),
     'yh_bn_l1_subgrad': (C.c_int, [_vp, C.c_int, C.c_int, _f32, _vp]),
+    'yh_eval_match': (C.c_int, [C.POINTER(EvalMatchDesc), _vp]),
     'yh_dw_wgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),
     'yh_dw_wgrad_workspace': (_i64, [C.POINTER(DwBwdDesc)]),
     'yh_dw_dgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),

@@ -2,7 +2,9 @@
 
 Same library signature and return contract as the reference's ``test.py:10-253`` (train.py calls it every epoch, the
 prune scripts call ``test(...)[0][2]`` for mAP), fresh code.  On a CUDA device the model forward and the NMS run on
-the HIP path (``models.Darknet`` / ``utils.utils.non_max_suppression``); matching and AP are host side.
+the HIP path (``models.Darknet`` / ``utils.utils.non_max_suppression``), and so does the matching of detections to labels: one launch
+and one host read per batch (``engine.evalmatch.match_batch``; ``YOLO_HIP_EVAL_MATCH=0`` keeps the per-image host loop, which is also
+what CPU tensors run).  AP is host side.
 """
 import argparse
 import glob
@@ -16,6 +18,7 @@ import torch.nn as nn
 from torch.utils.data import DataLoader
 
 from models import Darknet, attempt_download, load_darknet_weights
+from engine import evalmatch
 from utils import torch_utils
 from utils.datasets import LoadImagesAndLabels, LetterboxBatch
 from utils.parse_config import parse_data_cfg
@@ -53,6 +56,26 @@ def _match(pred, labels, whwh, iouv):
                 if len(claimed) == len(labels):
                     break
     return correct
+
+
+def host_stats(output, targets, height, width, iouv):
+    """The statistics of one batch by the per-image host loop (reference test.py:123-185): per image with detections
+    ``(correct, conf, cls, tcls)`` on the host, the empty entry for labels without detections; ``output`` is clipped in place.
+    What CPU tensors run, and CUDA tensors under ``YOLO_HIP_EVAL_MATCH=0`` (engine.evalmatch.match_batch otherwise)."""
+    niou = iouv.numel()
+    whwh = torch.tensor([width, height, width, height], dtype=torch.float32, device=targets.device)
+    stats = []
+    for si, pred in enumerate(output):
+        labels = targets[targets[:, 0] == si, 1:]
+        tcls = labels[:, 0].tolist() if len(labels) else []
+        if pred is None:
+            if len(labels):
+                stats.append((torch.zeros(0, niou, dtype=torch.bool), torch.Tensor(), torch.Tensor(), tcls))
+            continue
+        clip_coords(pred, (height, width))
+        correct = _match(pred, labels, whwh, iouv)
+        stats.append((correct.cpu(), pred[:, 4].cpu(), pred[:, 5].cpu(), tcls))
+    return stats
 
 
 def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, iou_thres=0.6, save_json=False, augment=False,
@@ -111,9 +134,9 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
             imgs = imgs.to(device).float() / 256.0      # uint8 -> [0, 1): the reference divides by 256 (test.py:96)
             if maxabsscaler:
                 imgs = imgs * 2 - 1
+        targets_host = targets                         # the loader's host copy: label counts and classes come from it
         targets = targets.to(device)
         nb, _, height, width = imgs.shape
-        whwh = torch.tensor([width, height, width, height], dtype=torch.float32, device=device)
         with torch.no_grad():
             t = torch_utils.time_synchronized()
             if not augment and not hasattr(model, 'hyp') and hasattr(model, 'hip_detect'):
@@ -131,29 +154,26 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
                 output = non_max_suppression(inf_out, conf_thres=conf_thres, iou_thres=iou_thres, multi_label=multi_label)
                 t_nms += torch_utils.time_synchronized() - t
 
-        for si, pred in enumerate(output):
-            labels = targets[targets[:, 0] == si, 1:]
-            tcls = labels[:, 0].tolist() if len(labels) else []
-            seen += 1
+        # clip, match and the statistics of the batch; `output` is clipped in place.  On a GPU: one launch, one host read (csrc/evalmatch.hip)
+        if evalmatch.enabled(device):
+            stats.extend(evalmatch.match_batch(output, targets_host, targets, height, width, iouv))
+        else:
+            stats.extend(host_stats(output, targets, height, width, iouv))
+        seen += len(output)
+        for si, pred in enumerate(output if save_json else ()):
             if pred is None:
-                if len(labels):
-                    stats.append((torch.zeros(0, niou, dtype=torch.bool), torch.Tensor(), torch.Tensor(), tcls))
                 continue
-            clip_coords(pred, (height, width))
-            if save_json:
-                image_id = Path(paths[si]).stem.split('_')[-1]
-                image_id = int(image_id) if image_id.isdigit() else Path(paths[si]).stem
-                box = pred[:, :4].clone()
-                if shapes[si] is not None:
-                    scale_coords(imgs[si].shape[1:], box, shapes[si][0], shapes[si][1])
-                box = xyxy2xywh(box)
-                box[:, :2] -= box[:, 2:] / 2
-                for row, b in zip(pred.tolist(), box.tolist()):
-                    cid = int(row[5])
-                    jdict.append({'image_id': image_id, 'category_id': coco91[cid] if cid < len(coco91) else cid,
-                                  'bbox': [round(x, 3) for x in b], 'score': round(row[4], 5)})
-            correct = _match(pred, labels, whwh, iouv)
-            stats.append((correct.cpu(), pred[:, 4].cpu(), pred[:, 5].cpu(), tcls))
+            image_id = Path(paths[si]).stem.split('_')[-1]
+            image_id = int(image_id) if image_id.isdigit() else Path(paths[si]).stem
+            box = pred[:, :4].clone()
+            if shapes[si] is not None:
+                scale_coords(imgs[si].shape[1:], box, shapes[si][0], shapes[si][1])
+            box = xyxy2xywh(box)
+            box[:, :2] -= box[:, 2:] / 2
+            for row, b in zip(pred.tolist(), box.tolist()):
+                cid = int(row[5])
+                jdict.append({'image_id': image_id, 'category_id': coco91[cid] if cid < len(coco91) else cid,
+                              'bbox': [round(x, 3) for x in b], 'score': round(row[4], 5)})
 
         if batch_i < 1 and plot:
             plot_images(imgs, targets, paths=paths, names=names, fname='test_batch%g_gt.jpg' % batch_i, is_gray_scale=is_gray_scale)

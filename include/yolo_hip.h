@@ -784,6 +784,40 @@ int yh_ptq_cos_search(const float* t, int64_t count, float scale0, int n, float 
 int yh_absmax(const float* t, int64_t count, void* ws, int64_t ws_bytes, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Quantization-aware training on the device (csrc/qat.hip; utils/quantized/quantized_google.py of this package calls these through
+ * engine/qat.py when its tensor is a dense fp32 GPU tensor).  All pointers are DEVICE pointers to fp32; nothing is read back.
+ * yh_qat_observe: minmax[0] = min(t), minmax[1] = max(t) in one pass (per-workgroup partials + one finishing wave) - the two
+ *   reductions of RangeTracker.forward, q_level 'L' (reference utils/quantized/quantized_google.py:24-32).  Exact, independent of
+ *   the order; a NaN anywhere gives NaN in both, as torch.min / torch.max do.  t: `count` elements of a dense tensor in any order;
+ *   ws: yh_qat_observe_workspace(count) bytes.
+ * yh_qat_range_update: one tracker step and (scale != NULL) one scale step, in place, one wave:
+ *   tracker YH_QAT_TRACK_GLOBAL   GlobalRangeTracker.update_range (:46-55), including its alias: after the first call the range is
+ *                                 min(0, min) / max(0, max) of the CURRENT tensor, not a running extreme;
+ *           YH_QAT_TRACK_AVERAGED AveragedRangeTracker.update_range (:70-77) with `momentum`;
+ *   `first` is the tracker's first_w / first_a buffer: read, and set to 1 by the first call;
+ *   asymmetric 0  SymmetricQuantizer.update_params (:178-196): scale = pow2(max(|min_val|, |max_val|)) / max(|q_lo|, |q_hi|), zero_point = 0;
+ *   asymmetric 1  AsymmetricQuantizer.update_params (:202-219): scale = pow2(max_val - min_val) / (q_hi - q_lo),
+ *                 zero_point = round_half_even(q_hi - max_val / scale);
+ *   [q_lo, q_hi] = [-2^(bits-1), 2^(bits-1) - 1] when is_signed, else [0, 2^bits - 1], 2 <= bits <= 24 (exact in fp32);  pow2(x) is the power of two nearest to x in
+ *   absolute distance, the lower on a tie (:189-194), taken from the bits of x: x = m 2^e, m in [0.5, 1): 2^e if m > 0.75 else
+ *   2^(e-1); pow2(0) = 0.  scale == NULL: tracker only (the shortcut modules' trackers, :896-899, :1130-1131, :1167).
+ * yh_qat_fake_quant_fwd: y = (clamp(r, lo, hi) - zp) * s with u = x / s + zp, r = sign(u) floor(|u| + 0.5) (:114-136, Round :81-87; the
+ *   clamp iff do_clamp), s = *scale, zp = *zero_point (NULL: 0); IEEE division, no contraction.  snapshot (NULL or float[2]) receives
+ *   {s, zp} for the backward; step (NULL or float[1]) is incremented by one - the quantiser's call counter (:152).
+ * yh_qat_fake_quant_bwd: dx = ((dy * s) * mask) / s, mask = lo <= r <= hi recomputed from x with snapshot's {s, zp} (false for NaN):
+ *   the straight-through chain autograd walks through dequantize, clamp, Round and quantize; dy under the mask for power-of-two s.
+ *   Without a clamp the backward is the identity and needs no launch.                                                         */
+enum { YH_QAT_TRACK_GLOBAL = 0, YH_QAT_TRACK_AVERAGED = 1 };
+int64_t yh_qat_observe_workspace(int64_t count);
+int yh_qat_observe(const float* t, int64_t count, void* ws, int64_t ws_bytes, float* minmax, void* stream);
+int yh_qat_range_update(const float* minmax, float* min_val, float* max_val, float* first, float* scale, float* zero_point,
+                        int tracker, double momentum, int asymmetric, int is_signed, int bits, void* stream);
+int yh_qat_fake_quant_fwd(const float* x, float* y, int64_t count, const float* scale, const float* zero_point, float lo, float hi,
+                          int do_clamp, float* snapshot, float* step, void* stream);
+int yh_qat_fake_quant_bwd(const float* x, const float* dy, float* dx, int64_t count, const float* snapshot, float lo, float hi,
+                          void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Plans: a recorded sequence of the launches above, replayed by one native call per forward (the
  * replacement for the per-layer Python dispatch loop of models.py:524-545).  Pointers that change
  * from call to call (network input, per-call outputs) are "slots": a fixup patches one pointer field

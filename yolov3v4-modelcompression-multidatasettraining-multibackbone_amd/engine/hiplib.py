@@ -209,6 +209,7 @@ class EvalMatchDesc(C.Structure):
                 ('ws_bytes', _i64), ('images', _i32), ('nt', _i32), ('total', _i32), ('niou', _i32), ('width', _f32), ('height', _f32)]
 
 
+QAT_TRACK_GLOBAL, QAT_TRACK_AVERAGED = 0, 1     # YH_QAT_TRACK_*: the tracker rule of yh_qat_range_update
 EVAL_MATCH_LDS_LABELS = 512     # YH_EVAL_MATCH_LDS_LABELS: labels of one image the kernel stages in LDS (more: its chunked form)
 
 
@@ -328,6 +329,11 @@ _SIGNATURES = {
     'yh_ptq_search_workspace': (_i64, [_i64]),
     'yh_ptq_cos_search': (C.c_int, [_vp, _i64, _f32, C.c_int, _f32, _f32, C.c_int, _vp, _i64, _vp, _vp, _vp]),
     'yh_absmax': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    'yh_qat_observe_workspace': (_i64, [_i64]),
+    'yh_qat_observe': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    'yh_qat_range_update': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp]),
+    'yh_qat_fake_quant_fwd': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _f32, _f32, C.c_int, _vp, _vp, _vp]),
+    'yh_qat_fake_quant_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _vp]),
     'yh_plan_create': (_vp, []),
     'yh_plan_destroy': (None, [_vp]),
     'yh_plan_add': (C.c_int, [_vp, C.c_int, _vp, C.c_int]),

@@ -62,7 +62,8 @@ def _takes_stream_pair(module):
 
 
 def _quantized_namespace(quantized):
-    """Lazy import of the reference's fake-quant operator classes (they run unmodified on top)."""
+    """Lazy import of the fake-quant operator classes: this package's own for 1 (BN-folding QAT) and 3 (COS-PTQ), the reference's
+    unmodified file for 2 (TPSQ) when a checkout is present."""
     if quantized == 1:
         import utils.quantized.quantized_google as q
     elif quantized == 2:
@@ -425,8 +426,9 @@ class Darknet(nn.Module):
         return torch.cat(y, 1), None
 
     def _use_hip(self, x):
-        # float graphs and the calibrated COS-PTQ graph (quantized == 3, eval) are lowered; the QAT research
-        # quantisers (1, 2) stay on the eager modules
+        # float graphs and the calibrated COS-PTQ graph (quantized == 3, eval) are lowered.  The QAT graphs (1, 2) stay on the eager
+        # modules: those of quantized == 1 (utils/quantized/quantized_google.py) run their quantisers as fused HIP passes
+        # (engine/qat.py) around torch convolutions, TPSQ (2) is the reference's eager arithmetic
         return x.is_cuda and not self.training and self.quantized in (-1, 3)
 
     def _use_hip_train(self, x):

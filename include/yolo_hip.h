@@ -818,6 +818,36 @@ int yh_qat_fake_quant_bwd(const float* x, const float* dy, float* dx, int64_t co
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * TPSQ, learnable power-of-two scales, on the device (csrc/tpsq.hip; utils/quantized/quantized_TPSQ.py of this package calls these
+ * through engine/tpsq.py when its tensor is a dense fp32 GPU tensor and its scale has one element).  All pointers are DEVICE pointers
+ * to fp32; nothing is read back.  qmul = 2^(bits-1) - 1, qdiv = 2^(bits-1), 2 <= bits <= 24; pow2 as above with pow2(+-0) = +0,
+ * pow2(+inf) = +inf, pow2(negative or NaN) = NaN; sign(v) = (0 < v) - (v < 0), 0 for a NaN.
+ * yh_tpsq_fake_quant_fwd: s0 = *scale; p = pow2(s0); *scale = p (Search_Pow2 leaves the snapped value in the parameter, reference
+ *   utils/quantized/quantized_TPSQ.py:37-42); snapshot[0] = s0, snapshot[1] = p; per element, IEEE division, no contraction (:84-102):
+ *     a = x + p;  b = x - p;  c = 0.5 * (|a| - |b|);  m = c * qmul;  q = m / p;  r = sign(q) * floor(|q| + 0.5);  y = (r * p) / qdiv
+ *   x, y: `count` elements of a dense tensor in any order.
+ * yh_tpsq_fake_quant_bwd: with {s0, p} = snapshot and a, b, m, r recomputed from x, autograd's chain operation for operation:
+ *     g_n = dy / qdiv;  g_q = g_n * p;  g_m = g_q / p;  g_d = (g_m * qmul) * 0.5;  g_a = g_d * sign(a);  g_b = (-g_d) * sign(b);
+ *     dx = g_a + g_b;   t1 = g_a;  t2 = -g_b;  t3 = (-g_q) * ((m / p) / p);  t4 = g_n * r
+ *   G_k = sum of t_k over the elements (per-workgroup partials in ws, one finishing wave, a fixed order: the same bits on every run,
+ *   no atomics), and *scale_grad = (((p / p) * G_4 + (p / p) * G_3) + (p / p) * G_2) + (p / s0) * G_1: Search_Pow2's backward (:48-51)
+ *   of the four applications of one quantiser call, of which only the first saw the raw value.  ws: yh_tpsq_grad_workspace(count) bytes.
+ * yh_tpsq_warmup_search: the 99-candidate search of the quantisers' first call (:262-282) in one pass.  step: one float, max(x) / 100
+ *   as the caller computed it.  Candidate i = 1 .. 99 has the scale step * i, which the chain snaps to pow2(step * i): one of
+ *   pow2(step) * 2^k, k <= 8.  The pass takes sum x^2 and per power sum x y_k, sum y_k^2 (y_k: the forward's y with p = that power;
+ *   products and sums in double); the finishing wave forms cos_k = <x, y_k> / (max(|x|, 1e-8) max(|y_k|, 1e-8)) rounded to fp32, walks
+ *   i = 1 .. 99 from max_metrics = -1, max_step = -5 with a strict > (the first maximum; a NaN never wins), and writes
+ *   *scale = step * max_step (not snapped) and *warmup += -1.  ws: yh_tpsq_warmup_workspace(count) bytes, 8-byte aligned.
+ * Return YH_EINVAL for a null pointer, count <= 0, bits out of range or an undersized workspace.                              */
+int yh_tpsq_fake_quant_fwd(const float* x, float* y, int64_t count, float* scale, int bits, float* snapshot, void* stream);
+int64_t yh_tpsq_grad_workspace(int64_t count);
+int yh_tpsq_fake_quant_bwd(const float* x, const float* dy, float* dx, int64_t count, const float* snapshot, int bits, void* ws,
+                           int64_t ws_bytes, float* scale_grad, void* stream);
+int64_t yh_tpsq_warmup_workspace(int64_t count);
+int yh_tpsq_warmup_search(const float* x, int64_t count, const float* step, int bits, void* ws, int64_t ws_bytes, float* scale,
+                          float* warmup, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Plans: a recorded sequence of the launches above, replayed by one native call per forward (the
  * replacement for the per-layer Python dispatch loop of models.py:524-545).  Pointers that change
  * from call to call (network input, per-call outputs) are "slots": a fixup patches one pointer field

@@ -334,6 +334,11 @@ _SIGNATURES = {
     'yh_qat_range_update': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _vp]),
     'yh_qat_fake_quant_fwd': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _f32, _f32, C.c_int, _vp, _vp, _vp]),
     'yh_qat_fake_quant_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _f32, _f32, _vp]),
+    'yh_tpsq_fake_quant_fwd': (C.c_int, [_vp, _vp, _i64, _vp, C.c_int, _vp, _vp]),
+    'yh_tpsq_grad_workspace': (_i64, [_i64]),
+    'yh_tpsq_fake_quant_bwd': (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp, _vp]),
+    'yh_tpsq_warmup_workspace': (_i64, [_i64]),
+    'yh_tpsq_warmup_search': (C.c_int, [_vp, _i64, _vp, C.c_int, _vp, _i64, _vp, _vp, _vp]),
     'yh_plan_create': (_vp, []),
     'yh_plan_destroy': (None, [_vp]),
     'yh_plan_add': (C.c_int, [_vp, C.c_int, _vp, C.c_int]),

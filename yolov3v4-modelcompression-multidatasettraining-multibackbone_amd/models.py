@@ -62,8 +62,7 @@ def _takes_stream_pair(module):
 
 
 def _quantized_namespace(quantized):
-    """Lazy import of the fake-quant operator classes: this package's own for 1 (BN-folding QAT) and 3 (COS-PTQ), the reference's
-    unmodified file for 2 (TPSQ) when a checkout is present."""
+    """Lazy import of this package's fake-quant operator classes: 1 BN-folding QAT, 2 TPSQ, 3 COS-PTQ."""
     if quantized == 1:
         import utils.quantized.quantized_google as q
     elif quantized == 2:
@@ -195,7 +194,8 @@ def create_modules(module_defs, img_size, cfg, quantized, quantizer_output, laye
             if quantized == -1:
                 modules = FeatureConcat(layers=layers, groups=grouped)
             else:
-                ns = _quantized_namespace(quantized)
+                # TPSQ (2) has no concat of its own: it takes the Google one next to the plain Shortcut (reference models.py:253-267, :273)
+                ns = _quantized_namespace(1 if quantized == 2 else quantized)
                 cls = ns.COSPTQuantizedFeatureConcat if quantized == 3 else ns.QuantizedFeatureConcat
                 modules = cls(layers=layers, groups=grouped, bits=a_bit, quantizer_output=quantizer_output,
                               reorder=reorder, TM=TM, TN=TN, name="{:04d}".format(i) + "_" + kind[:4],
@@ -427,8 +427,8 @@ class Darknet(nn.Module):
 
     def _use_hip(self, x):
         # float graphs and the calibrated COS-PTQ graph (quantized == 3, eval) are lowered.  The QAT graphs (1, 2) stay on the eager
-        # modules: those of quantized == 1 (utils/quantized/quantized_google.py) run their quantisers as fused HIP passes
-        # (engine/qat.py) around torch convolutions, TPSQ (2) is the reference's eager arithmetic
+        # modules, which run their quantisers as fused HIP passes around torch convolutions: utils/quantized/quantized_google.py on
+        # engine/qat.py for quantized == 1, utils/quantized/quantized_TPSQ.py on engine/tpsq.py for TPSQ (2)
         return x.is_cuda and not self.training and self.quantized in (-1, 3)
 
     def _use_hip_train(self, x):

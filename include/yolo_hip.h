@@ -735,6 +735,43 @@ typedef struct yh_resize_desc {
 } yh_resize_desc;
 int yh_resize_bilinear(const yh_resize_desc* d, void* stream);
 
+/* Test-time augmentation (csrc/tta.hip, csrc/nms.hip): `--augment` of detect.py / test.py, reference models.py:477-506 - the frame, a
+ * flipped 0.83x copy and a 0.67x copy go through the network, the copies' boxes are mapped back and all rows are concatenated in front
+ * of the NMS.  Added without a change of YH_ABI_VERSION: no struct or existing entry changed.
+ *
+ * yh_tta_view builds ONE view in one launch: torch_utils.scale_img(x.flip(3) if flip else x, ratio, same_shape=False), i.e. bilinear
+ * resize of src (n, c, ih, iw) to rh x rw in the top-left corner of dst (n, c, oh, ow), pad_value everywhere else (rows >= rh, columns
+ * >= rw).  Inside rh x rw the arithmetic is yh_resize_bilinear's formula above with scale_h = (float)ih / (float)rh and scale_w =
+ * (float)iw / (float)rw computed by the CALLER in fp32, every product and sum rounded to fp32 once; with flip = 1 source column x is
+ * read as iw - 1 - x, which is the resize of src.flip(3).  rh == ih, rw == iw, flip = 0 returns the input bits (finite inputs).
+ * 1 <= rh <= oh, 1 <= rw <= ow, flip in {0, 1}.  src and dst are dense, 4-byte aligned and may not overlap; dst may point at an image
+ * offset inside a larger (g * n, c, oh, ow) batch - that is how views of equal padded shape are stacked for one forward.  One wave per
+ * 64-pixel segment of an output row, no LDS, no atomics, no workspace.                                                                */
+typedef struct yh_tta_view_desc {
+    const float* src;            /* [n][c][ih][iw]                                                                   */
+    float* dst;                  /* [n][c][oh][ow]                                                                   */
+    int32_t n, c, ih, iw, oh, ow;
+    int32_t rh, rw;              /* resized content: int(ih * ratio), int(iw * ratio)                                */
+    int32_t flip;                /* 1: mirror the source in x                                                        */
+    float scale_h, scale_w;      /* (float)ih / (float)rh, (float)iw / (float)rw                                     */
+    float pad_value;             /* scale_img: 0.447                                                                 */
+} yh_tta_view_desc;
+int yh_tta_view(const yh_tta_view_desc* d, void* stream);
+/* yh_yolo_decode_candidates with the de-augmentation of models.py:493-495 between decode and filter, in this order:
+ *   1  cx, cy, w, h  are each divided by `scale` - correctly rounded fp32 division (what the reference's CPU `/=` computes; a
+ *      multiplication by the reciprocal differs from it in about one value of five)
+ *   2  if flip_w >= 0:  cx = flip_w - cx      (flip_w: the ORIGINAL frame's width, not the view's padded width)
+ *   3  the width / height window, xywh -> xyxy and the score tests of yh_yolo_decode_candidates, unchanged
+ * `d` describes the view's head: p / n narrowed to the view's images inside a stacked batch, row_off shifted by the rows of the earlier
+ * views, rows_total the rows of all views, so that key = row * nc + cls indexes the reference's torch.cat(y, 1).  scale > 0.
+ * scale == 1 and flip_w < 0 give yh_yolo_decode_candidates' records bit for bit.                                                     */
+int yh_yolo_decode_candidates_tta(const yh_decode_desc* d, float scale, float flip_w, float conf_thres, int multi_label,
+                                  const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream);
+/* Steps 1 and 2 above in place on rows [row0, row0 + nrows) of every image of a decoded fp32 tensor io (n, rows_total, no): the
+ * two-pass path's de-augmentation (ATen's GPU division by a scalar multiplies by a reciprocal - this one divides, so both paths share
+ * one arithmetic).  Columns 4.. are not touched.  0 <= row0, row0 + nrows <= rows_total, no >= 4, scale > 0.                          */
+int yh_tta_deaugment(float* io, int n, int rows_total, int no, int row0, int nrows, float scale, float flip_w, void* stream);
+
 /* Input pipeline on the device, second slice: ONE training item = 4-image mosaic -> random affine warp (bilinear, constant
  * border) -> HSV augmentation -> left-right flip -> planar CHW uint8 or x / divisor float.  Replaces utils/datasets.py
  * load_mosaic + random_affine + augment_hsv + the flip / transpose of __getitem__ (reference datasets.py:553-608, 649-715, 534-550,

@@ -121,10 +121,15 @@ __global__ __launch_bounds__(256) void nms_candidates_kernel(const float* __rest
 // the records equal the two-pass path's as a set, and the sort makes the rest identical.
 __device__ __forceinline__ float dec_sigmoid(float v) { return rcp_fast(1.f + exp_fast(-v)); }
 
-template <bool ML>
+// TTA (test-time augmentation, reference models.py:477-506): the rows of a scaled / flipped view are mapped back to the frame between
+// decode and filter - cx, cy, w, h divided by the view's scale (IEEE fp32 division, as the reference's CPU `/=`), cx mirrored about
+// the ORIGINAL frame width when flip_w >= 0 (models.py:493-495) - so the (n, rows, 5 + nc) tensors of the three passes and their
+// torch.cat are never written either.  TTA = false compiles the two operations out: the plain entry's records do not change by a bit.
+template <bool ML, bool TTA>
 __global__ __launch_bounds__(256) void yolo_decode_candidates_kernel(const yh_decode_desc d, const float conf,
                                                                      const uint8_t* __restrict__ class_mask, float* cand,
-                                                                     int32_t* count, const int cap) {
+                                                                     int32_t* count, const int cap, const float scale,
+                                                                     const float flip_w) {
     __shared__ float anchor[16];
     if (threadIdx.x < 16) anchor[threadIdx.x] = threadIdx.x < 8 ? d.anchor_w[threadIdx.x & 7] : d.anchor_h[threadIdx.x & 7];
     __syncthreads();
@@ -145,8 +150,12 @@ __global__ __launch_bounds__(256) void yolo_decode_candidates_kernel(const yh_de
         if (__ballot(live) == 0ull) continue;                // wave-uniform: emit() needs every lane of a wave
         float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
         if (live) {
-            const float cx = (dec_sigmoid(src[0]) + (float)x) * d.stride, cy = (dec_sigmoid(src[1]) + (float)y) * d.stride;
-            const float w = (exp_fast(src[2]) * anchor[a]) * d.stride, h = (exp_fast(src[3]) * anchor[8 + a]) * d.stride;
+            float cx = (dec_sigmoid(src[0]) + (float)x) * d.stride, cy = (dec_sigmoid(src[1]) + (float)y) * d.stride;
+            float w = (exp_fast(src[2]) * anchor[a]) * d.stride, h = (exp_fast(src[3]) * anchor[8 + a]) * d.stride;
+            if constexpr (TTA) {
+                cx = cx / scale; cy = cy / scale; w = w / scale; h = h / scale;
+                if (flip_w >= 0.f) cx = flip_w - cx;
+            }
             live = w > kMinWH && w < kMaxWH && h > kMinWH && h < kMaxWH;
             x1 = cx - w / 2; y1 = cy - h / 2; x2 = cx + w / 2; y2 = cy + h / 2;
         }
@@ -697,11 +706,29 @@ extern "C" int yh_yolo_decode_candidates(const yh_decode_desc* d, float conf_thr
     long g = (total + 255) / 256;
     if (g > 65536) g = 65536;
     if (multi_label)
-        hipLaunchKernelGGL(yolo_decode_candidates_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d, conf_thres,
-                           class_mask, cand, count, cap);
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<true, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, 1.f, -1.f);
     else
-        hipLaunchKernelGGL(yolo_decode_candidates_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d, conf_thres,
-                           class_mask, cand, count, cap);
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<false, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, 1.f, -1.f);
+    return check_launch();
+}
+
+extern "C" int yh_yolo_decode_candidates_tta(const yh_decode_desc* d, float scale, float flip_w, float conf_thres, int multi_label,
+                                             const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream) {
+    if (!d || !d->p || !count || d->n <= 0 || d->ny <= 0 || d->nx <= 0 || d->na <= 0 || d->na > 8 || d->no <= 5 || cap < 0) return YH_EINVAL;
+    if (!(scale > 0.f) || flip_w != flip_w) return YH_EINVAL;
+    if (cand && !aligned16(cand)) return YH_EALIGN;
+    if ((long)d->rows_total * (d->no - 5) > 0x7fffffffL) return YH_EUNSUPPORTED;      // the key is a 32-bit row * nc + cls
+    const long total = (long)d->n * d->na * d->ny * d->nx;
+    long g = (total + 255) / 256;
+    if (g > 65536) g = 65536;
+    if (multi_label)
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<true, true>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, scale, flip_w);
+    else
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<false, true>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, scale, flip_w);
     return check_launch();
 }
 

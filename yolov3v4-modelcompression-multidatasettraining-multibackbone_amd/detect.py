@@ -68,14 +68,16 @@ def detect(opt, save_img=True):
             x = x.unsqueeze(0)
         t1 = torch_utils.time_synchronized()
         with torch.no_grad():
-            if opt.augment or not hasattr(model, 'hip_detect'):
+            # --augment goes through the engine call as well (YOLO_HIP_TTA=0: the three forwards, torch's de-augmentation and the
+            # row-tensor NMS as two calls)
+            if (opt.augment and os.environ.get('YOLO_HIP_TTA', '1') == '0') or not hasattr(model, 'hip_detect'):
                 pred = model(x, augment=opt.augment)[0]
                 t2 = torch_utils.time_synchronized()
                 pred = non_max_suppression(pred.float(), opt.conf_thres, opt.iou_thres, multi_label=False, classes=opt.classes,
                                            agnostic=opt.agnostic_nms)
             else:      # forward + NMS as one engine call (models.Darknet.hip_detect: same boxes, no decoded tensor in between)
                 pred = model.hip_detect(x, opt.conf_thres, opt.iou_thres, multi_label=False, classes=opt.classes,
-                                        agnostic=opt.agnostic_nms)
+                                        agnostic=opt.agnostic_nms, augment=opt.augment)
                 t2 = torch_utils.time_synchronized()
         for det in pred:
             save_path = str(Path(out) / Path(path).name)

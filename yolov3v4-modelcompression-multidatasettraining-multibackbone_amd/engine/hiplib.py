@@ -166,6 +166,11 @@ class ResizeDesc(C.Structure):
                 ('scale_h', _f32), ('scale_w', _f32)]
 
 
+class TtaViewDesc(C.Structure):
+    _fields_ = [('src', _vp), ('dst', _vp), ('n', _i32), ('c', _i32), ('ih', _i32), ('iw', _i32), ('oh', _i32), ('ow', _i32),
+                ('rh', _i32), ('rw', _i32), ('flip', _i32), ('scale_h', _f32), ('scale_w', _f32), ('pad_value', _f32)]
+
+
 class MosaicDesc(C.Structure):
     _fields_ = [('src', _vp * 4), ('dst', _vp), ('inv', C.c_double * 6), ('hsv_gain', C.c_double * 3),
                 ('src_h', _i32 * 4), ('src_w', _i32 * 4), ('src_pitch', _i32 * 4),
@@ -325,6 +330,9 @@ _SIGNATURES = {
     'yh_nchw_to_nhwc': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'yh_letterbox_fwd': (C.c_int, [C.POINTER(LetterboxDesc), _vp]),
     'yh_resize_bilinear': (C.c_int, [C.POINTER(ResizeDesc), _vp]),
+    'yh_tta_view': (C.c_int, [C.POINTER(TtaViewDesc), _vp]),
+    'yh_yolo_decode_candidates_tta': (C.c_int, [C.POINTER(DecodeDesc), _f32, _f32, _f32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    'yh_tta_deaugment': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp]),
     'yh_mosaic_affine_hsv': (C.c_int, [C.POINTER(MosaicDesc), _vp]),
     'yh_ptq_search_workspace': (_i64, [_i64]),
     'yh_ptq_cos_search': (C.c_int, [_vp, _i64, _f32, C.c_int, _f32, _f32, C.c_int, _vp, _i64, _vp, _vp, _vp]),

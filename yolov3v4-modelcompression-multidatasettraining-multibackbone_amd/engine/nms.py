@@ -60,23 +60,31 @@ class _Rows:
 
 
 class _Heads:
-    """... or the head convolutions' outputs themselves (yh_yolo_decode_candidates: decode and filter in one pass, DarknetEngine.detect)."""
+    """... or the head convolutions' outputs themselves (yh_yolo_decode_candidates: decode and filter in one pass, DarknetEngine.detect).
+    An entry is a descriptor, or ``(descriptor, scale, flip_w)`` for the head of an augmented view whose rows are mapped back to the
+    frame inside the pass (yh_yolo_decode_candidates_tta, DarknetEngine.detect with ``augment``)."""
 
     def __init__(self, descs, n, rows, nc, device):
         self.descs, self.n, self.rows, self.nc, self.device = descs, n, rows, nc, device
 
     def candidates(self, lib, conf, ml, cmask, cand, count, cap, stream):
         for d in self.descs:
+            if isinstance(d, tuple):
+                d, scale, flip_w = d
+                hiplib.check(lib.yh_yolo_decode_candidates_tta(C.byref(d), scale, flip_w, conf, ml, hiplib.ptr(cmask), hiplib.ptr(cand),
+                                                               hiplib.ptr(count), cap, stream), 'decode + de-augment + candidates')
+                continue
             hiplib.check(lib.yh_yolo_decode_candidates(C.byref(d), conf, ml, hiplib.ptr(cmask), hiplib.ptr(cand), hiplib.ptr(count), cap,
                                                        stream), 'decode + candidates')
 
     def images(self, i0, i1):
         part = []
-        for d in self.descs:
+        for entry in self.descs:
+            d = entry[0] if isinstance(entry, tuple) else entry
             e = hiplib.DecodeDesc.from_buffer_copy(d)
             e.p = d.p + i0 * d.ny * d.nx * d.ldp * 4          # fp32 NHWC with pitch ldp, image-major
             e.n = i1 - i0
-            part.append(e)
+            part.append((e,) + entry[1:] if isinstance(entry, tuple) else e)
         return _Heads(part, i1 - i0, self.rows, self.nc, self.device)
 
 

@@ -23,6 +23,7 @@ The reference executes the graph with a per-layer Python loop over ``nn.Module``
 Nothing here computes activations with torch: torch supplies device memory and the stream.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -31,14 +32,34 @@ import torch.nn as nn
 
 from . import hiplib
 from .hiplib import (ConvDesc, StemDesc, PoolDesc, CopyDesc, AddDesc, DecodeDesc, DwDesc, SeDesc, QCopyDesc, QPoolDesc,
-                     QAddDesc)
+                     QAddDesc, TtaViewDesc)
 
 SLOT_INPUT, SLOT_IO, SLOT_RAW0 = 0, 1, 2
 ALIGN_C = 8  # physical channel granularity of every NHWC buffer (16 bytes of fp16)
+TTA_VIEWS = ((1.0, 0), (0.83, 1), (0.67, 0))   # (ratio, flip) of the test-time augmentation passes (reference models.py:484-488)
+TTA_PAD = 0.447                                # torch_utils.scale_img's border value
 
 
 def _round_up(a, b):
     return (a + b - 1) // b * b
+
+
+def tta_views(h, w):
+    """The passes of ``model(x, augment=True)`` for an h x w frame: per view ``(ratio, flip, rh, rw, oh, ow)`` - the resized content
+    ``int(h * s), int(w * s)`` inside a ``ceil(h * s / 64) * 64`` frame (``torch_utils.scale_img(..., same_shape=False)``); the
+    first view is the frame itself."""
+    out = [(1.0, 0, h, w, h, w)]
+    for s, flip in TTA_VIEWS[1:]:
+        out.append((s, flip, int(h * s), int(w * s), math.ceil(h * s / 64) * 64, math.ceil(w * s / 64) * 64))
+    return out
+
+
+def tta_groups(views):
+    """Views of equal padded shape run as ONE forward, stacked along the batch in view order: ``[[view index, ...], ...]``."""
+    groups = {}
+    for k, v in enumerate(views):
+        groups.setdefault(v[4:6], []).append(k)
+    return list(groups.values())
 
 
 class Value:
@@ -713,12 +734,17 @@ class DarknetEngine:
         feats = self._features(plan) if self.return_features else []
         return io, tuple(raws), feats
 
-    def detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False):
+    def detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False, augment=False):
         """``non_max_suppression(model(x)[0], ...)`` (reference detect.py:104-109) without the decoded (N, rows, 5 + nc) tensor: the plan
         runs up to the head convolutions, ``yh_yolo_decode_candidates`` decodes only the rows whose objectness passes ``conf_thres``
         straight into the NMS candidate records, the remaining NMS steps are ``engine/nms.py``'s.  Same list of (n_i, 6) tensors,
-        bit for bit (tests/test_gpu_nms.py).  Small batches keep the hipGraph replay of ``__call__`` (launch-bound there)."""
+        bit for bit (tests/test_gpu_nms.py).  Small batches keep the hipGraph replay of ``__call__`` (launch-bound there).
+
+        ``augment``: ``non_max_suppression(model(x, augment=True)[0], ...)`` - test-time augmentation - the same way
+        (``_detect_augmented``)."""
         from . import nms as hnms
+        if augment:
+            return self._detect_augmented(x, conf_thres, iou_thres, multi_label, classes, agnostic)
         x, plan = self._plan_for(x)
         N = x.shape[0]
         lib, handle = self.lib, plan['handle']
@@ -734,6 +760,108 @@ class DarknetEngine:
         lib.yh_plan_bind_slot(handle, SLOT_INPUT, x.data_ptr())
         hiplib.check(lib.yh_plan_run_range(handle, 0, plan['first_decode_op'], hiplib.stream_ptr()), 'yh_plan_run_range')
         return hnms.non_max_suppression_heads(plan['decode_descs'], N, plan['rows'], plan['no'] - 5, x.device, conf_thres, iou_thres,
+                                              multi_label, classes, agnostic)
+
+    # ------------------------------------------------------------------------ test-time augmentation
+    def _tta_inputs(self, x):
+        """The augmented views of ``x`` as network inputs: ``(x, views, [(members, xg), ...])`` with one ``(g * N, C, H', W')`` batch
+        ``xg`` per group of views that share a padded shape (``yh_tta_view`` writes view ``members[j]`` at image offset ``j * N``).
+        The frame itself is passed through when it is alone in its group."""
+        if x.dim() != 4:
+            raise ValueError('expected an (N, C, H, W) batch')
+        x = x.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        N, Cin, H, W = x.shape
+        views = tta_views(H, W)
+        if min(min(v[2:4]) for v in views) < 1 or N < 1:
+            raise ValueError('augmented inference: a %d x %d frame has an empty 0.67x view' % (H, W))
+        out = []
+        with hiplib.on_device(x):
+            for members in tta_groups(views):
+                if members == [0]:
+                    out.append((members, x))
+                    continue
+                oh, ow = views[members[0]][4:6]
+                xg = torch.empty((len(members) * N, Cin, oh, ow), dtype=torch.float32, device=x.device)
+                for j, k in enumerate(members):
+                    _, flip, rh, rw = views[k][:4]
+                    d = TtaViewDesc(src=hiplib.ptr(x), dst=hiplib.ptr(xg, j * N * Cin * oh * ow), n=N, c=Cin, ih=H, iw=W, oh=oh, ow=ow,
+                                    rh=rh, rw=rw, flip=flip, scale_h=float(np.float32(H) / np.float32(rh)),
+                                    scale_w=float(np.float32(W) / np.float32(rw)), pad_value=TTA_PAD)
+                    hiplib.check(self.lib.yh_tta_view(C.byref(d), hiplib.stream_ptr()), 'yh_tta_view')
+                out.append((members, xg))
+        return x, views, out
+
+    @staticmethod
+    def _tta_transform(view, W):
+        """(scale, flip_w) of a view as the de-augmentation entries take them: the ratio in fp32, the ORIGINAL width or -1."""
+        return float(np.float32(view[0])), float(W) if view[1] else -1.0
+
+    def forward_augmented(self, x):
+        """``model(x, augment=True)[0]`` (reference models.py:477-506) as a tensor: one forward per group of views, the scaled views'
+        rows mapped back in place by ``yh_tta_deaugment`` (IEEE division, like the fused path and the reference's CPU arithmetic),
+        concatenated in view order.  The two-pass form of ``detect(..., augment=True)``."""
+        x, views, inputs = self._tta_inputs(x)
+        N, W = x.shape[0], x.shape[3]
+        keep = self.want_raw
+        self.want_raw = False
+        parts = [None] * len(views)
+        try:
+            for members, xg in inputs:
+                io = self(xg)[0]
+                rows, no = io.shape[1], io.shape[2]
+                for j, k in enumerate(members):
+                    if k:
+                        scale, flip_w = self._tta_transform(views[k], W)
+                        hiplib.check(self.lib.yh_tta_deaugment(hiplib.ptr(io, j * N * rows * no), N, rows, no, 0, rows, scale, flip_w,
+                                                               hiplib.stream_ptr()), 'yh_tta_deaugment')
+                    parts[k] = io[j * N:(j + 1) * N]
+        finally:
+            self.want_raw = keep
+        return torch.cat(parts, 1)
+
+    def _detect_augmented(self, x, conf_thres, iou_thres, multi_label, classes, agnostic):
+        """``detect`` over the three views: every group's plan runs up to its head convolutions, and ONE candidate pass per (view, head)
+        decodes, maps back and filters (``yh_yolo_decode_candidates_tta``) with keys that index the reference's ``torch.cat(y, 1)`` -
+        neither the three decoded tensors nor their concatenation are written.  The groups' plans are distinct and stay resident
+        until the NMS returns: its retry and count-first passes read the heads again."""
+        from . import nms as hnms
+        if x.dim() != 4:
+            raise ValueError('expected an (N, C, H, W) batch')
+        groups = tta_groups(tta_views(x.shape[2], x.shape[3]))
+        N = x.shape[0]
+        graph = x.is_cuda and hasattr(self.lib, 'yh_plan_graph_launch') and any(0 < len(m) * N <= self.graph_max_batch for m in groups)
+        if graph or self.return_features or os.environ.get('YOLO_HIP_FUSED_DETECT', '1') == '0' or len(groups) > self.max_plans:
+            return hnms.non_max_suppression(self.forward_augmented(x), conf_thres, iou_thres, multi_label, classes, agnostic)
+        x, views, inputs = self._tta_inputs(x)
+        W = x.shape[3]
+        ran = []
+        for members, xg in inputs:
+            xg, plan = self._plan_for(xg)
+            self.lib.yh_plan_bind_slot(plan['handle'], SLOT_INPUT, xg.data_ptr())
+            hiplib.check(self.lib.yh_plan_run_range(plan['handle'], 0, plan['first_decode_op'], hiplib.stream_ptr()), 'yh_plan_run_range')
+            ran.append((members, xg, plan))
+        rows_of = {k: plan['rows'] for members, _, plan in ran for k in members}
+        total = sum(rows_of.values())
+        no = ran[0][2]['no']
+        if total * (no - 5) > 0x7fffffff:
+            raise ValueError('augmented inference: %d rows x %d classes do not fit the 32-bit candidate key' % (total, no - 5))
+        entries = [None] * len(views)
+        for members, _, plan in ran:
+            if plan['no'] != no:
+                raise ValueError('the view plans disagree on the class count')
+            for j, k in enumerate(members):
+                off = sum(rows_of[i] for i in range(k))
+                scale, flip_w = self._tta_transform(views[k], W)
+                heads = []
+                for d in plan['decode_descs']:
+                    e = DecodeDesc.from_buffer_copy(d)
+                    e.p = d.p + j * N * d.ny * d.nx * d.ldp * 4      # this view's images inside the stacked batch
+                    e.n, e.rows_total, e.row_off = N, total, off + d.row_off
+                    heads.append((e, scale, flip_w))
+                entries[k] = heads
+        return hnms.non_max_suppression_heads([h for heads in entries for h in heads], N, total, no - 5, x.device, conf_thres, iou_thres,
                                               multi_label, classes, agnostic)
 
     def _plan_for(self, x):

@@ -531,14 +531,22 @@ class Darknet(nn.Module):
         with _on_device(x.device):   # kernels launch on the current device / stream: make it the input's
             return eng(x)
 
-    def hip_detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False):
+    def hip_detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False, augment=False):
         """``non_max_suppression(self(x)[0], conf_thres, iou_thres, ...)`` - what detect.py does with a batch (reference
         detect.py:104-109) - as ONE engine call: on the HIP path the decoded (N, rows, 5 + nc) tensor is never written, the yolo
         heads' outputs are decoded and filtered in one pass straight into the NMS candidate records (engine/plan.py ``detect``).
-        Same result, bit for bit; on the eager path (CPU, training mode) it is literally the two calls."""
+        Same result, bit for bit; on the eager path (CPU, training mode) it is literally the two calls.
+
+        ``augment``: the same for ``self(x, augment=True)[0]`` (``--augment``: the frame, a flipped 0.83x and a 0.67x view) - the
+        views are built by one kernel each, views of equal shape share a forward, and the mapping back to the frame happens inside
+        the candidate pass (engine/plan.py ``_detect_augmented``).  Bit for bit the NMS of ``DarknetEngine.forward_augmented(x)``;
+        against ``self(x, augment=True)`` on a GPU the rows agree within that call's bounds (tests/test_gpu_network.py), not bit for
+        bit: the views come from ``yh_tta_view`` instead of ATen's bilinear kernel, and the divisions are IEEE divisions like the
+        CPU's where ATen's GPU ``/=`` multiplies by a reciprocal."""
         from utils.utils import non_max_suppression
         if not self._use_hip(x):
-            return non_max_suppression(self(x)[0], conf_thres, iou_thres, multi_label=multi_label, classes=classes, agnostic=agnostic)
+            return non_max_suppression(self(x, augment=True)[0] if augment else self(x)[0], conf_thres, iou_thres, multi_label=multi_label,
+                                       classes=classes, agnostic=agnostic)
         from engine.plan import DarknetEngine
         eng = self.__dict__.get('_hip_engine')
         precision = 'int8' if self.quantized == 3 else self.hip_precision
@@ -549,7 +557,7 @@ class Darknet(nn.Module):
         # plan, buffer and hipGraph on each alternation; plan.detect takes its two-pass branch when features are on
         eng.return_features = bool(getattr(self, 'hip_return_features', False))
         with _on_device(x.device):
-            return eng.detect(x, conf_thres, iou_thres, multi_label, classes, agnostic)
+            return eng.detect(x, conf_thres, iou_thres, multi_label, classes, agnostic, augment=augment)
 
     def _forward_eager(self, x, augment=False, verbose=False):
         img_size = x.shape[-2:]

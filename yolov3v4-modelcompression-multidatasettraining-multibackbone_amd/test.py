@@ -139,10 +139,11 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
         nb, _, height, width = imgs.shape
         with torch.no_grad():
             t = torch_utils.time_synchronized()
-            if not augment and not hasattr(model, 'hyp') and hasattr(model, 'hip_detect'):
+            if not (augment and os.environ.get('YOLO_HIP_TTA', '1') == '0') and not hasattr(model, 'hyp') and hasattr(model, 'hip_detect'):
                 # stand-alone evaluation (no validation loss wanted): forward + NMS as one engine call - on the HIP path the decoded
-                # (N, rows, 5 + nc) tensor is never written (models.Darknet.hip_detect; same detections bit for bit)
-                output = model.hip_detect(imgs, conf_thres, iou_thres, multi_label=multi_label)
+                # (N, rows, 5 + nc) tensor is never written (models.Darknet.hip_detect; same detections bit for bit).  --augment too
+                # (YOLO_HIP_TTA=0: the three forwards, torch's de-augmentation and the row-tensor NMS as two calls)
+                output = model.hip_detect(imgs, conf_thres, iou_thres, multi_label=multi_label, augment=augment)
                 t_inf += torch_utils.time_synchronized() - t
                 fused_calls += 1
             else:

@@ -274,7 +274,14 @@ typedef struct yh_qadd_desc {
     int32_t c, ldx, lda, ldy;
     float rx, ra, scale_x, scale_a, inv_scale_sum;
 } yh_qadd_desc;
-int yh_qadd(const yh_qadd_desc* d, void* stream);
+int yh_qadd(const yh_qadd_desc* d, void* stream);   /* c <= ldx, lda, ldy: a row never runs into the next pixel */
+/* QuantizedShortcut_max of the QAT family (quantized_google.py, eval): like yh_qadd, but the operands are clamped to the int8 range
+ * after their re-quantisation, as every fake-quant of that module does:
+ *   xq = clamp(round(x * rx)), aq = clamp(round(a * ra)),  y = clamp(round((xq * scale_x + aq * scale_a) * inv_scale_sum))
+ * The clamp can act only when rx > 1 or ra > 1 (an operand on a coarser grid than the shortcut's); with both ratios <= 1 the two
+ * entries compute the same bytes.  Same descriptor, same alignment rules, one thread per 16 channels.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+int yh_qadd_clamped(const yh_qadd_desc* d, void* stream);
 /* Device self-test of the Mish the int8 epilogues use (csrc/common.h mish_for_grid: a cheap form, the exact form wherever the
  * result lies next to a rounding tie of the activation grid) over the float bit patterns [bits0, bits1), |v| <= 64:
  * out[0] = values whose int8 grid index differs from the exact form's (must be 0), out[1] = largest relative difference of the
@@ -894,7 +901,7 @@ enum { YH_OP_CONV = 1, YH_OP_STEM = 2, YH_OP_POOL = 3, YH_OP_COPY = 4, YH_OP_ADD
        YH_OP_SE = 8, YH_OP_QCOPY = 9, YH_OP_QPOOL = 10, YH_OP_QADD = 11, YH_OP_BN_STATS = 12, YH_OP_BN_FINALIZE = 13,
        YH_OP_BN_ACT_FWD = 14, YH_OP_BN_BWD_REDUCE = 15, YH_OP_BN_BWD_APPLY = 16, YH_OP_WGRAD = 17, YH_OP_STEM_WGRAD = 18,
        YH_OP_DILATE2 = 19, YH_OP_UPSAMPLE2_BWD = 20, YH_OP_CAST_F32 = 21, YH_OP_NCHW_TO_NHWC = 22, YH_OP_POOL_BWD = 23, YH_OP_PACK_BATCH = 24, YH_OP_DW_WGRAD = 25, YH_OP_DW_DGRAD = 26,
-       YH_OP_SE_BWD = 27, YH_OP_STEM_BWD = 28 };
+       YH_OP_SE_BWD = 27, YH_OP_STEM_BWD = 28, YH_OP_QADD_CLAMPED = 29 /* yh_qadd_desc through yh_qadd_clamped */ };
 typedef struct yh_pack_batch_desc { const yh_pack_item* items; int32_t n_items; } yh_pack_batch_desc;
 typedef struct yh_layout_desc { const float* x; void* y; int32_t n, c, h, w_in, c_pad, ldy, dtype; } yh_layout_desc;
 

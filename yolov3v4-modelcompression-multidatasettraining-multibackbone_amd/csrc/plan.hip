@@ -64,7 +64,7 @@ size_t desc_size(int kind) {
         case YH_OP_SE: return sizeof(yh_se_desc);
         case YH_OP_QCOPY: return sizeof(yh_qcopy_desc);
         case YH_OP_QPOOL: return sizeof(yh_pool_desc);
-        case YH_OP_QADD: return sizeof(yh_qadd_desc);
+        case YH_OP_QADD: case YH_OP_QADD_CLAMPED: return sizeof(yh_qadd_desc);
         case YH_OP_BN_STATS: case YH_OP_BN_FINALIZE: case YH_OP_BN_ACT_FWD: case YH_OP_BN_BWD_REDUCE: case YH_OP_BN_BWD_APPLY:
             return sizeof(yh_bn_desc);
         case YH_OP_WGRAD: case YH_OP_STEM_WGRAD: return sizeof(yh_wgrad_desc);
@@ -93,6 +93,7 @@ int launch(int kind, const AnyDesc& d, void* stream) {
         case YH_OP_QCOPY: return yh_qcopy(&d.qcopy, stream);
         case YH_OP_QPOOL: return yh_qpool(&d.pool, stream);
         case YH_OP_QADD: return yh_qadd(&d.qadd, stream);
+        case YH_OP_QADD_CLAMPED: return yh_qadd_clamped(&d.qadd, stream);
         case YH_OP_BN_STATS: return yh_bn_stats(&d.bn, stream);
         case YH_OP_BN_FINALIZE: return yh_bn_finalize(&d.bn, stream);
         case YH_OP_BN_ACT_FWD: return yh_bn_act_fwd(&d.bn, stream);

@@ -84,6 +84,9 @@ __global__ __launch_bounds__(256) void qpool_kernel(const yh_pool_desc d) {
     }
 }
 
+// CLAMP_OPS: the operands are clamped to the int8 range after their re-quantisation (QuantizedShortcut_max of the QAT family,
+// quantized_google.py _merge: every fake-quant of that module clamps).  A compile-time flag: the <false> form is yh_qadd's kernel as it was.
+template <bool CLAMP_OPS>
 __global__ __launch_bounds__(256) void qadd_kernel(const yh_qadd_desc d) {
     const int cg = d.c / 16;
     const long total = d.pixels * cg;
@@ -98,8 +101,14 @@ __global__ __launch_bounds__(256) void qadd_kernel(const yh_qadd_desc d) {
         B16 o;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const float xq = rnd_away((float)vx.v[e] * d.rx) * d.scale_x;
-            const float aq = rnd_away((float)va.v[e] * d.ra) * d.scale_a;
+            float xr = rnd_away((float)vx.v[e] * d.rx);
+            float ar = rnd_away((float)va.v[e] * d.ra);
+            if (CLAMP_OPS) {
+                xr = clamp_i8(xr);
+                ar = clamp_i8(ar);
+            }
+            const float xq = xr * d.scale_x;
+            const float aq = ar * d.scale_a;
             o.v[e] = (int8_t)(int)clamp_i8(rnd_away((xq + aq) * d.inv_scale_sum));
         }
         st16(y + pix * d.ldy + g * 16, o);
@@ -167,11 +176,26 @@ extern "C" int yh_qmish_selftest(uint32_t bits0, uint32_t bits1, float inv_s, ui
     return check_launch();
 }
 
-extern "C" int yh_qadd(const yh_qadd_desc* d, void* stream) {
+static int qadd_check(const yh_qadd_desc* d) {
     if (!d || !d->x || !d->a || !d->y || d->pixels <= 0 || d->c <= 0) return YH_EINVAL;
     if (!(d->rx > 0.f) || !(d->ra > 0.f) || !(d->scale_x > 0.f) || !(d->scale_a > 0.f) || !(d->inv_scale_sum > 0.f)) return YH_EINVAL;
     if (d->c % 16 || d->ldx % 16 || d->lda % 16 || d->ldy % 16 || !aligned16(d->x) || !aligned16(d->a) || !aligned16(d->y)) return YH_EALIGN;
+    if (d->c > d->ldx || d->c > d->lda || d->c > d->ldy) return YH_EINVAL;
+    return YH_OK;
+}
+
+extern "C" int yh_qadd(const yh_qadd_desc* d, void* stream) {
+    const int rc = qadd_check(d);
+    if (rc != YH_OK) return rc;
     const long total = d->pixels * (d->c / 16);
-    hipLaunchKernelGGL(qadd_kernel, dim3(grid_q(total)), dim3(256), 0, (hipStream_t)stream, *d);
+    hipLaunchKernelGGL(qadd_kernel<false>, dim3(grid_q(total)), dim3(256), 0, (hipStream_t)stream, *d);
+    return check_launch();
+}
+
+extern "C" int yh_qadd_clamped(const yh_qadd_desc* d, void* stream) {
+    const int rc = qadd_check(d);
+    if (rc != YH_OK) return rc;
+    const long total = d->pixels * (d->c / 16);
+    hipLaunchKernelGGL(qadd_kernel<true>, dim3(grid_q(total)), dim3(256), 0, (hipStream_t)stream, *d);
     return check_launch();
 }

@@ -91,6 +91,10 @@ class QAddDesc(C.Structure):
                 ('rx', _f32), ('ra', _f32), ('scale_x', _f32), ('scale_a', _f32), ('inv_scale_sum', _f32)]
 
 
+class QAddClampedDesc(QAddDesc):
+    """Same layout as QAddDesc; a distinct Python type so plans record it as YH_OP_QADD_CLAMPED (yh_qadd_clamped)."""
+
+
 class QPoolDesc(PoolDesc):
     """Same layout as PoolDesc; a distinct Python type so plans record it as YH_OP_QPOOL."""
 
@@ -256,13 +260,15 @@ class CastDesc(C.Structure):
 OP_BN_STATS, OP_BN_FINALIZE, OP_BN_ACT_FWD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY = 12, 13, 14, 15, 16
 OP_WGRAD, OP_STEM_WGRAD, OP_DILATE2, OP_UPSAMPLE2_BWD, OP_CAST_F32, OP_NCHW_TO_NHWC, OP_POOL_BWD, OP_PACK_BATCH = 17, 18, 19, 20, 21, 22, 23, 24
 OP_DW_WGRAD, OP_DW_DGRAD, OP_SE_BWD, OP_STEM_BWD = 25, 26, 27, 28
+OP_QADD_CLAMPED = 29
 
 OP_KIND = {BnStatsDesc: OP_BN_STATS, BnFinalizeDesc: OP_BN_FINALIZE, BnActFwdDesc: OP_BN_ACT_FWD,
            BnBwdReduceDesc: OP_BN_BWD_REDUCE, BnBwdApplyDesc: OP_BN_BWD_APPLY, WgradDesc: OP_WGRAD,
            StemWgradDesc: OP_STEM_WGRAD, DilateDesc: OP_DILATE2, UpsampleBwdDesc: OP_UPSAMPLE2_BWD, CastDesc: OP_CAST_F32, LayoutDesc: OP_NCHW_TO_NHWC, PoolBwdDesc: OP_POOL_BWD, PackBatchDesc: OP_PACK_BATCH, DwWgradDesc: OP_DW_WGRAD, DwDgradDesc: OP_DW_DGRAD,
            SeBwdDesc: OP_SE_BWD, StemBwdDesc: OP_STEM_BWD,
            ConvDesc: OP_CONV, StemDesc: OP_STEM, PoolDesc: OP_POOL, CopyDesc: OP_COPY, AddDesc: OP_ADD,
-           DecodeDesc: OP_DECODE, DwDesc: OP_DW, SeDesc: OP_SE, QCopyDesc: OP_QCOPY, QPoolDesc: OP_QPOOL, QAddDesc: OP_QADD}
+           DecodeDesc: OP_DECODE, DwDesc: OP_DW, SeDesc: OP_SE, QCopyDesc: OP_QCOPY, QPoolDesc: OP_QPOOL, QAddDesc: OP_QADD,
+           QAddClampedDesc: OP_QADD_CLAMPED}
 
 _SIGNATURES = {
     'yh_abi_version': (C.c_int, []),
@@ -287,6 +293,7 @@ _SIGNATURES = {
     'yh_qcopy': (C.c_int, [C.POINTER(QCopyDesc), _vp]),
     'yh_qpool': (C.c_int, [C.POINTER(PoolDesc), _vp]),
     'yh_qadd': (C.c_int, [C.POINTER(QAddDesc), _vp]),
+    'yh_qadd_clamped': (C.c_int, [C.POINTER(QAddDesc), _vp]),
     'yh_copy_channels': (C.c_int, [C.POINTER(CopyDesc), _vp]),
     'yh_add_channels': (C.c_int, [C.POINTER(AddDesc), _vp]),
     'yh_yolo_decode': (C.c_int, [C.POINTER(DecodeDesc), _vp]),

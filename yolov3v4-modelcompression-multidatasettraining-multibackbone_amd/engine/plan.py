@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import hiplib
 from .hiplib import (ConvDesc, StemDesc, PoolDesc, CopyDesc, AddDesc, DecodeDesc, DwDesc, SeDesc, QCopyDesc, QPoolDesc,
-                     QAddDesc, TtaViewDesc)
+                     QAddDesc, QAddClampedDesc, TtaViewDesc)
 
 SLOT_INPUT, SLOT_IO, SLOT_RAW0 = 0, 1, 2
 ALIGN_C = 8  # physical channel granularity of every NHWC buffer (16 bytes of fp16)
@@ -127,15 +127,168 @@ def _activation_of(block):
 _ACT_BY_NAME = {'leaky': 'leaky', 'relu6': 'relu6', 'h_swish': 'h_swish', 'relu': 'relu', 'mish': 'mish', 'linear': 'linear'}
 
 
+# The int8 engine executes two module families with the same eval arithmetic: the calibrated COS-PTQ graph (quantized == 3,
+# utils/quantized/quantized_ptq_cos.py) and the BN-folding QAT graph (quantized == 1, utils/quantized/quantized_google.py).  What
+# differs between them sits in the small functions below (duck-typed by class name, like the rest of the lowering); _build_values,
+# _place and _pack_qconv are shared.
+_COS_CONV = 'BNFold_COSPTQuantizedConv2d_For_FPGA'
+_QAT_CONV = 'BNFold_QuantizedConv2d_For_FPGA'
+_COS_SHORTCUTS = ('COSPTQuantizedShortcut_min', 'COSPTQuantizedShortcut_max')
+_QAT_SHORTCUTS = ('QuantizedShortcut_min', 'QuantizedShortcut_max')
+_QUANT_CONCATS = ('COSPTQuantizedFeatureConcat', 'QuantizedFeatureConcat')
+
+
 def _quant_conv_info(conv):
-    """(act code, slope, s_w, s_a) of a calibrated BNFold_COSPTQuantizedConv2d_For_FPGA (duck-typed)."""
-    if not getattr(conv, 'quantized', False):
+    """(act code, slope, s_w, s_a) of a calibrated BNFold_COSPTQuantizedConv2d_For_FPGA or of a BNFold_QuantizedConv2d_For_FPGA."""
+    if conv.__class__.__name__ == _COS_CONV and not getattr(conv, 'quantized', False):
         raise RuntimeError('HIP int8 engine: quantised conv has not been calibrated (run the PTQ calibration first)')
     name = _ACT_BY_NAME.get(conv.activate)
     if name is None:
         raise NotImplementedError('HIP int8 engine: activation %r' % conv.activate)
     slope = 0.25 if getattr(conv, 'maxabsscaler', False) else 0.1
     return hiplib.ACT_CODES[name], slope, float(conv.weight_quantizer.scale), float(conv.activation_quantizer.scale)
+
+
+def _quant_conv_grid(conv):
+    """(weight, bias) of a quantised conv on their grids, in real units, fp32 on the module's device.  The COS-PTQ conv stores them
+    (``q_weight`` / ``q_bias``).  The QAT conv folds BatchNorm with the running statistics and quantises on every forward
+    (quantized_google.py forward, eval branch); the same is done here with the module's own pure methods - NOT the quantisers'
+    ``forward``, which advances ``step`` and re-calibrates in training mode - so these are the eager path's weights by construction."""
+    if hasattr(conv, 'q_weight'):
+        return conv.q_weight.detach().float().contiguous(), conv.q_bias.detach().float().contiguous()
+    with torch.no_grad():
+        w, b = conv.BN_fuse()
+        grid = lambda q, t: q.dequantize(q.clamp(q.round(q.quantize(t))))
+        w = grid(conv.weight_quantizer, w)
+        b = torch.zeros(conv.out_channels, device=w.device) if b is None else grid(conv.bias_quantizer, b)
+    return w.detach().float().contiguous(), b.detach().float().contiguous()
+
+
+def _quant_shortcut_info(module):
+    """(scale_x, scale_a, scale_sum, operands clamped?) of a quantised shortcut.  COS-PTQ: three buffers, operands re-quantised
+    without clamp.  QAT ``_min``: both operands go to ``input_scale`` without clamp, the sum to ``scale``.  QAT ``_max``: one ``scale``
+    for all three, and every fake-quant of the module clamps - the operands too."""
+    name = module.__class__.__name__
+    if name in _COS_SHORTCUTS:
+        return float(module.scale_x), float(module.scale_a), float(module.scale_sum), False
+    if name == 'QuantizedShortcut_min':
+        return float(module.input_scale), float(module.input_scale), float(module.scale), False
+    if name == 'QuantizedShortcut_max':
+        return float(module.scale), float(module.scale), float(module.scale), True
+    raise NotImplementedError('HIP int8 engine: %s is not a quantised shortcut' % name)
+
+
+def _quant_concat_scale(module):
+    """The one scale every input of a quantised concat is re-quantised to (both families keep it in ``scale``)."""
+    return float(module.scale)
+
+
+def _quant_sources(block):
+    """The tensors a quantised block's packed weights and plan constants were computed from (``_current_signature``), or None for a
+    block of no quantised family.  The current objects are read on every call: ``update_params`` REBINDS the scale buffers."""
+    if isinstance(block, nn.Sequential) and len(block) and hasattr(block[0], 'q_weight'):
+        c = block[0]
+        return [c.q_weight, c.q_bias, c.weight_quantizer.scale, c.activation_quantizer.scale]
+    if isinstance(block, nn.Sequential) and len(block) and block[0].__class__.__name__ == _QAT_CONV:
+        c = block[0]
+        return [t for t in (c.weight, c.bias, c.gamma, c.beta, c.running_mean, c.running_var) if t is not None] + \
+            [c.weight_quantizer.scale, c.bias_quantizer.scale, c.activation_quantizer.scale]
+    if hasattr(block, 'scale_sum'):
+        return [block.scale_x, block.scale_a, block.scale_sum]
+    if hasattr(block, 'float_max_list'):
+        return [block.scale]
+    name = block.__class__.__name__
+    if name == 'QuantizedShortcut_min':
+        return [block.input_scale, block.scale]
+    if name == 'QuantizedShortcut_max':
+        return [block.scale]
+    return None
+
+
+def _is_pow2(s):
+    return math.isfinite(s) and s > 0 and math.frexp(s)[0] == 0.5
+
+
+def qat_int8_reason(model):
+    """Why the ``quantized == 1`` graph ``model`` cannot run on the int8 engine: ``(block index, text)``, or None when it can.
+
+    The ONE place that decides it: ``models.Darknet`` asks before it builds an engine (a graph that does not qualify stays on the
+    eager modules), and ``DarknetEngine(precision='int8')`` raises ``NotImplementedError`` with the block index.  The engine's eval
+    arithmetic is 8-bit signed symmetric with one power-of-two scale per tensor, so a graph qualifies when every conv has
+    ``a_bits == w_bits == 8``, symmetric per-tensor quantisers with zero ``zero_point`` and finite, positive power-of-two scales
+    (a fresh model has ``scale == 0``), no depthwise or squeeze-excite block, and unweighted single-source shortcuts over equal
+    widths.  All buffers are read with one host transfer."""
+    defs, mods = model.module_defs, model.module_list
+    scales, zeros, widths = [], [], []      # (block, tensor) pairs checked after the one read
+
+    def quantizer(i, q, what):
+        if getattr(q, 'asymmetric', False) or not q.sign:
+            return i, '%s quantiser is asymmetric' % what
+        if q.bits != 8:
+            return i, '%s quantiser has %d bits' % (what, q.bits)
+        if not q._per_tensor() or q.zero_point.numel() != 1:
+            return i, '%s quantiser is per channel' % what
+        scales.append((i, q.scale))
+        zeros.append((i, q.zero_point))
+        return None
+
+    for i, (mdef, m) in enumerate(zip(defs, mods)):
+        kind, name = mdef['type'], m.__class__.__name__
+        prev = widths[-1] if widths else 3
+        if kind == 'convolutional':
+            c = m[0] if isinstance(m, nn.Sequential) and len(m) else None
+            if c.__class__.__name__ != _QAT_CONV:
+                return i, 'not a BNFold_QuantizedConv2d_For_FPGA'
+            if c.groups != 1:
+                return i, 'grouped convolution'
+            if c.a_bits != 8 or c.w_bits != 8:
+                return i, 'a_bits %d, w_bits %d' % (c.a_bits, c.w_bits)
+            if c.activate not in _ACT_BY_NAME:
+                return i, 'activation %r' % c.activate
+            for q, what in ((c.weight_quantizer, 'weight'), (c.bias_quantizer, 'bias'), (c.activation_quantizer, 'activation')):
+                bad = quantizer(i, q, what)
+                if bad:
+                    return bad
+            widths.append(c.out_channels)
+        elif kind in ('depthwise', 'se'):
+            return i, '%s block' % kind
+        elif kind == 'shortcut':
+            if name not in _QAT_SHORTCUTS:
+                return i, 'shortcut module %s' % name
+            if m.weight or len(m.layers) != 1:
+                return i, 'weighted or multi-source shortcut'
+            if m.bits != 8:
+                return i, 'shortcut has %d bits' % m.bits
+            j = i + m.layers[0] if m.layers[0] < 0 else m.layers[0]
+            if not 0 <= j < i or widths[j] != prev:
+                return i, 'shortcut over different widths'
+            scales.extend((i, t) for t in _quant_sources(m))
+            widths.append(prev)
+        elif kind == 'route':
+            if name != 'QuantizedFeatureConcat':
+                return i, 'route module %s' % name
+            src = [widths[i + l if l < 0 else l] for l in m.layers]
+            if m.multiple:
+                if m.bits != 8:
+                    return i, 'concat has %d bits' % m.bits
+                scales.append((i, m.scale))
+                widths.append(sum(src))
+            else:
+                widths.append(prev // 2 if m.groups else src[0])
+        elif kind in ('maxpool', 'upsample', 'yolo', 'reorg3d'):
+            widths.append(prev)
+        else:
+            return i, 'block type %r' % kind
+    if not scales:
+        return 0, 'no quantised block'
+    flat = torch.cat([t.detach().reshape(-1)[:1].float() for _, t in scales + zeros]).tolist()
+    for (i, _), s in zip(scales, flat):
+        if not _is_pow2(s):
+            return i, 'scale %r is not a finite positive power of two (not calibrated?)' % s
+    for (i, _), z in zip(zeros, flat[len(scales):]):
+        if z != 0:
+            return i, 'zero_point %r' % z
+    return None
 
 
 def _conv_parts(block):
@@ -163,7 +316,10 @@ class DarknetEngine:
         self.dtype = {'fp16': torch.float16, 'fp32': torch.float32, 'int8': torch.int8}[precision]
         self.kstep = {'fp16': 32, 'fp32': 16, 'int8': 64}[precision]
         self.align = 16 if precision == 'int8' else ALIGN_C
-        self.q = precision == 'int8'  # PTQ eval graph: modules are the reference's COSPTQuantized* classes
+        # int8: the eval graph of a quantised module family - the reference's COSPTQuantized* classes (quantized == 3) or the QAT
+        # classes of quantized_google.py (quantized == 1), which must qualify (qat_int8_reason, checked whenever a plan is built)
+        self.q = precision == 'int8'
+        self.qat = self.q and getattr(model, 'quantized', None) == 1
         self.want_raw = True
         self.return_features = False
         self.force_tile = int(os.environ.get('YOLO_HIP_TILE', '0'))  # A/B profiling knob; 0 = library heuristic
@@ -183,6 +339,10 @@ class DarknetEngine:
         model = self.model
         defs, mods, routs = model.module_defs, model.module_list, model.routs
         L = len(mods)
+        if self.qat:
+            reason = qat_int8_reason(model)
+            if reason is not None:
+                raise NotImplementedError('HIP int8 engine: QAT graph does not qualify, block %d: %s' % reason)
         Value.ALIGN = self.align
         x0 = Value('input', Cin, H, W)
         values, heads = [x0], []
@@ -223,8 +383,8 @@ class DarknetEngine:
                     raise NotImplementedError('HIP engine: unsupported conv geometry at block %d' % i)
                 Ho, Wo = (cur.H + 2 * p - k) // s + 1, (cur.W + 2 * p - k) // s + 1
                 if self.q:
-                    if conv.__class__.__name__ != 'BNFold_COSPTQuantizedConv2d_For_FPGA':
-                        raise NotImplementedError('HIP int8 engine: block %d is not a COS-PTQ quantised conv' % i)
+                    if conv.__class__.__name__ not in (_COS_CONV, _QAT_CONV):
+                        raise NotImplementedError('HIP int8 engine: block %d is not a COS-PTQ or QAT quantised conv' % i)
                     act, slope, s_w, s_a = _quant_conv_info(conv)
                 else:
                     act, slope = _activation_of(module)
@@ -239,9 +399,8 @@ class DarknetEngine:
                     skip.add(i + 1)
                     hidden = True
                     if self.q:   # quantised shortcut in the conv epilogue: the value leaves on the SUM grid
-                        sc = mods[i + 1]
-                        v.qadd = (float(sc.scale_x), float(sc.scale_a), float(sc.scale_sum))
-                        v.act_scale, v.scale = v.scale, float(sc.scale_sum)
+                        v.qadd = _quant_shortcut_info(mods[i + 1])[:3]
+                        v.act_scale, v.scale = v.scale, v.qadd[2]
                 elif nxt == 'upsample' and not routs[i] and not keep and int(defs[i + 1]['stride']) == 2:
                     v.ups = 2
                     v.H, v.W = 2 * Ho, 2 * Wo
@@ -297,8 +456,10 @@ class DarknetEngine:
                         v.segs.extend((off + st, ln) for st, ln in s.segs)
                         off += s.c_phys
                     v.c_phys = off
-                    if self.q:  # COSPTQuantizedFeatureConcat: every input is re-quantised to one shared scale
-                        v.scale = float(module.scale)
+                    if self.q:  # (COSPT)QuantizedFeatureConcat: every input is re-quantised to one shared scale
+                        if cname not in _QUANT_CONCATS:
+                            raise NotImplementedError('HIP int8 engine: route %d is a %s' % (i, cname))
+                        v.scale = _quant_concat_scale(module)
                         if not v.scale > 0:
                             raise RuntimeError('HIP int8 engine: route %d has no calibrated scale' % i)
                     values.append(v)
@@ -326,15 +487,16 @@ class DarknetEngine:
                 else:
                     cur = ref(i, layers[0])
             elif kind == 'shortcut' and self.q:
-                if cname not in ('COSPTQuantizedShortcut_min', 'COSPTQuantizedShortcut_max') or getattr(module, 'weight', False) \
-                        or len(module.layers) != 1:
+                if cname not in _COS_SHORTCUTS + _QAT_SHORTCUTS or getattr(module, 'weight', False) or len(module.layers) != 1:
                     raise NotImplementedError('HIP int8 engine: shortcut form at block %d' % i)
                 other = ref(i, module.layers[0])
                 if other.C != cur.C or not cur.is_dense() or not other.is_dense():
                     raise NotImplementedError('HIP int8 engine: channel-mismatched shortcut (block %d)' % i)
-                v = Value('qadd', cur.C, cur.H, cur.W, block=i, a=cur, b=other, scale_x=float(module.scale_x),
-                          scale_a=float(module.scale_a))
-                v.scale = float(module.scale_sum)
+                if cur.scale is None or other.scale is None:
+                    raise NotImplementedError('HIP int8 engine: shortcut %d reads a tensor that is not on an int8 grid' % i)
+                sx, sa, ssum, clamp_ops = _quant_shortcut_info(module)
+                v = Value('qadd', cur.C, cur.H, cur.W, block=i, a=cur, b=other, scale_x=sx, scale_a=sa, clamp_ops=clamp_ops)
+                v.scale = ssum
                 values.append(v)
                 cur = v
             elif kind == 'shortcut':
@@ -368,7 +530,7 @@ class DarknetEngine:
 
     def _fusable_shortcut(self, j, conv_value, outs):
         module = self.model.module_list[j]
-        names = ('COSPTQuantizedShortcut_min', 'COSPTQuantizedShortcut_max') if self.q else ('Shortcut',)
+        names = _COS_SHORTCUTS + _QAT_SHORTCUTS if self.q else ('Shortcut',)
         if module.__class__.__name__ not in names or getattr(module, 'weight', False) or len(module.layers) != 1:
             return False
         l = module.layers[0]
@@ -379,6 +541,12 @@ class DarknetEngine:
             # the int8 epilogue carries the shortcut for the compile-time activations only; the routed tensor must be on a grid
             ok = (conv_value.act in (hiplib.ACT_CODES['linear'], hiplib.ACT_CODES['leaky'], hiplib.ACT_CODES['mish'])
                   and other.scale is not None and conv_value.C % 16 == 0 and os.environ.get('YOLO_HIP_FUSE_QADD', '1') != '0')
+        if ok and self.q:
+            # the epilogue has no operand clamp.  A shortcut whose operands are clamped (QAT QuantizedShortcut_max) may ride in it only
+            # when rx <= 1 and ra <= 1: an int8 operand times such a ratio stays inside [-128, 127], so the clamp cannot act.
+            # Otherwise the shortcut stays a separate yh_qadd_clamped op.
+            sx, sa, _, clamp_ops = _quant_shortcut_info(module)
+            ok = not clamp_ops or (conv_value.scale <= sx and other.scale <= sa)
         return ok
 
     def _place(self, values):
@@ -403,13 +571,9 @@ class DarknetEngine:
     def _source_tensors(self):
         out = []
         for block in self.model.module_list:
-            if self.q and isinstance(block, nn.Sequential) and len(block) and hasattr(block[0], 'q_weight'):
-                c = block[0]
-                out.extend((c.q_weight, c.q_bias, c.weight_quantizer.scale, c.activation_quantizer.scale))
-            elif self.q and hasattr(block, 'scale_sum'):
-                out.extend((block.scale_x, block.scale_a, block.scale_sum))
-            elif self.q and hasattr(block, 'float_max_list'):
-                out.append(block.scale)
+            quant = _quant_sources(block) if self.q else None
+            if quant is not None:
+                out.extend(quant)
             elif isinstance(block, nn.Sequential) and len(block) and isinstance(block[0], nn.Conv2d):
                 conv, bn = _conv_parts(block)
                 out.extend(t for t in (conv.weight, conv.bias) if t is not None)
@@ -466,11 +630,11 @@ class DarknetEngine:
         return slot
 
     def _pack_qconv(self, v):
-        """int8 image of a calibrated COS-PTQ conv: grid weights from q_weight / s_w, bias = q_bias in real units."""
+        """int8 image of a quantised conv: grid weights from the real-unit grid weight / s_w, bias on its grid in real units
+        (``_quant_conv_grid``: stored by a COS-PTQ conv, computed here from the live parameters of a QAT conv)."""
         conv = v.conv
-        dev = conv.q_weight.device
-        qw = conv.q_weight.detach().float().contiguous()
-        qb = conv.q_bias.detach().float().contiguous()
+        qw, qb = _quant_conv_grid(conv)
+        dev = qw.device
         P = hiplib.ptr
         slot = self._packed.get(v.block)
         if v.src.kind == 'input':  # float frames in: the stem kernel multiplies real-valued (de-quantised) weights
@@ -649,9 +813,10 @@ class DarknetEngine:
                 add(QCopyDesc(x=P(s.storage, s.c_off), y=y, n=N, h=s.H, w_in=s.W, c=s.c_phys, ups=v.ups, ldx=s.ld, ldy=v.ld,
                               ratio=1.0), 'ups%d' % v.block)
             elif v.kind == 'qadd':
-                add(QAddDesc(x=P(v.a.storage, v.a.c_off), a=P(v.b.storage, v.b.c_off), y=y, pixels=N * v.H * v.W, c=v.c_phys,
-                             ldx=v.a.ld, lda=v.b.ld, ldy=v.ld, rx=v.a.scale / v.scale_x, ra=v.b.scale / v.scale_a,
-                             scale_x=v.scale_x, scale_a=v.scale_a, inv_scale_sum=1.0 / v.scale), 'qadd%d' % v.block)
+                cls = QAddClampedDesc if v.clamp_ops else QAddDesc     # operands clamped after re-quantisation: yh_qadd_clamped
+                add(cls(x=P(v.a.storage, v.a.c_off), a=P(v.b.storage, v.b.c_off), y=y, pixels=N * v.H * v.W, c=v.c_phys,
+                        ldx=v.a.ld, lda=v.b.ld, ldy=v.ld, rx=v.a.scale / v.scale_x, ra=v.b.scale / v.scale_a,
+                        scale_x=v.scale_x, scale_a=v.scale_a, inv_scale_sum=1.0 / v.scale), 'qadd%d' % v.block)
             elif v.kind == 'copy':
                 s = v.src
                 add(CopyDesc(x=P(s.storage, s.c_off), y=y, n=N, h=s.H, w_in=s.W, c=s.c_phys, ups=v.ups, ldx=s.ld,
@@ -885,7 +1050,9 @@ class DarknetEngine:
             self._signature = sig
         elif sig != self._signature:
             old_shapes = [s[2] for s in self._signature]
-            if old_shapes != [s[2] for s in sig]:  # graph widths changed (pruning): start over
+            # graph widths changed (pruning): start over.  So does a QAT int8 engine: its plans carry the scales as launch constants
+            # (acc_scale, out_scale, the re-quantisation ratios), and a re-calibration moves them
+            if old_shapes != [s[2] for s in sig] or self.qat:
                 self._drop_plans()
                 self._packed = {}
                 self._signature = sig

@@ -363,7 +363,8 @@ class _HipTrainSegment(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
-_ENGINE_ATTRS = ('_hip_engine', '_hip_train_engine')   # ctypes handles + device buffers: never copied or pickled
+# ctypes handles + device buffers: never copied or pickled; the QAT engine decision and its quantiser list are rebuilt with them
+_ENGINE_ATTRS = ('_hip_engine', '_hip_train_engine', '_qat_int8', '_qat_quantizers')
 
 
 class Darknet(nn.Module):
@@ -426,10 +427,51 @@ class Darknet(nn.Module):
         return torch.cat(y, 1), None
 
     def _use_hip(self, x):
-        # float graphs and the calibrated COS-PTQ graph (quantized == 3, eval) are lowered.  The QAT graphs (1, 2) stay on the eager
-        # modules, which run their quantisers as fused HIP passes around torch convolutions: utils/quantized/quantized_google.py on
-        # engine/qat.py for quantized == 1, utils/quantized/quantized_TPSQ.py on engine/tpsq.py for TPSQ (2)
-        return x.is_cuda and not self.training and self.quantized in (-1, 3)
+        # float graphs, the calibrated COS-PTQ graph (quantized == 3, eval) and a qualifying QAT graph (quantized == 1, eval: the same
+        # 8-bit power-of-two arithmetic, engine/plan.py qat_int8_reason) are lowered.  QAT training, QAT graphs that do not qualify
+        # and TPSQ (2: its plain Shortcut sums two int8-grid tensors without rounding or clamp, which is not an int8 tensor) stay on
+        # the eager modules, which run their quantisers as fused HIP passes around torch convolutions:
+        # utils/quantized/quantized_google.py on engine/qat.py, utils/quantized/quantized_TPSQ.py on engine/tpsq.py
+        if not x.is_cuda or self.training:
+            return False
+        return self.quantized in (-1, 3) or (self.quantized == 1 and self._qat_on_int8())
+
+    def _qat_on_int8(self):
+        """Does this ``quantized == 1`` model evaluate on the int8 engine?  Decided from the model's own state (bit widths, quantiser
+        kinds, calibrated power-of-two scales: engine/plan.py ``qat_int8_reason``), cached, and dropped wherever the engine is.
+        ``YOLO_HIP_QAT_INT8=0`` keeps the eager modules (tests, tools/qat_int8_timing.py)."""
+        if os.environ.get('YOLO_HIP_QAT_INT8', '1') == '0':
+            return False
+        use = self.__dict__.get('_qat_int8')
+        if use is None:
+            from engine.plan import qat_int8_reason
+            use = self.__dict__['_qat_int8'] = qat_int8_reason(self) is None
+        return use
+
+    def _hip_eval_precision(self):
+        return 'int8' if self.quantized in (1, 3) else self.hip_precision
+
+    def _qat_advance_steps(self, forwards=1):
+        """An eager eval forward of a QAT graph advances ``step`` of every conv's three quantisers by one, and the freeze schedule of a
+        later training epoch reads those counters: the engine path does the same with one multi-tensor add.  The quantisers' host
+        mirrors of ``step`` must not go stale: one that exists moves with its buffer (dropping it would cost the next eager forward or
+        training step one host read per quantiser), one that does not is read when it is first needed.  No other buffer changes."""
+        if self.quantized != 1:
+            return
+        qs = self.__dict__.get('_qat_quantizers')
+        if qs is None:
+            qs = self.__dict__['_qat_quantizers'] = [q for m in self.module_list if isinstance(m, nn.Sequential) and len(m)
+                                                     and hasattr(m[0], 'activation_quantizer')
+                                                     for q in (m[0].weight_quantizer, m[0].bias_quantizer, m[0].activation_quantizer)]
+        with torch.no_grad():
+            torch._foreach_add_([q.step for q in qs], float(forwards))
+        for q in qs:
+            if q._mirror is not None:
+                q._mirror += forwards
+
+    def _drop_hip_engines(self):
+        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self.__dict__['_qat_int8'] = self.__dict__['_qat_quantizers'] = None
 
     def _use_hip_train(self, x):
         # training step on the HIP kernels (engine/train.py, engine/padded.py): every float graph on a GPU.  A cfg that path
@@ -520,7 +562,7 @@ class Darknet(nn.Module):
     def _forward_hip(self, x):
         from engine.plan import DarknetEngine  # raises if libyolo_hip.so is missing: no fallback
         eng = self.__dict__.get('_hip_engine')
-        precision = 'int8' if self.quantized == 3 else self.hip_precision
+        precision = self._hip_eval_precision()
         if eng is None or eng.precision != precision:
             eng = DarknetEngine(self, precision=precision)
             self.__dict__['_hip_engine'] = eng
@@ -529,7 +571,9 @@ class Darknet(nn.Module):
         # callers that read it (test.py's validation loss); detect.py reads model(img)[0] alone and switches it off
         eng.want_raw = bool(self.__dict__.get('hip_return_raw', True))
         with _on_device(x.device):   # kernels launch on the current device / stream: make it the input's
-            return eng(x)
+            out = eng(x)
+        self._qat_advance_steps()
+        return out
 
     def hip_detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False, augment=False):
         """``non_max_suppression(self(x)[0], conf_thres, iou_thres, ...)`` - what detect.py does with a batch (reference
@@ -549,7 +593,7 @@ class Darknet(nn.Module):
                                        classes=classes, agnostic=agnostic)
         from engine.plan import DarknetEngine
         eng = self.__dict__.get('_hip_engine')
-        precision = 'int8' if self.quantized == 3 else self.hip_precision
+        precision = self._hip_eval_precision()
         if eng is None or eng.precision != precision:
             eng = DarknetEngine(self, precision=precision)
             self.__dict__['_hip_engine'] = eng
@@ -557,7 +601,9 @@ class Darknet(nn.Module):
         # plan, buffer and hipGraph on each alternation; plan.detect takes its two-pass branch when features are on
         eng.return_features = bool(getattr(self, 'hip_return_features', False))
         with _on_device(x.device):
-            return eng.detect(x, conf_thres, iou_thres, multi_label, classes, agnostic, augment=augment)
+            det = eng.detect(x, conf_thres, iou_thres, multi_label, classes, agnostic, augment=augment)
+        self._qat_advance_steps(3 if augment else 1)      # model(x, augment=True) is three eager forwards
+        return det
 
     def _forward_eager(self, x, augment=False, verbose=False):
         img_size = x.shape[-2:]
@@ -613,7 +659,7 @@ class Darknet(nn.Module):
                         break
             fused_list.append(block)
         self.module_list = fused_list
-        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self._drop_hip_engines()
 
     def info(self, verbose=False):
         torch_utils.model_info(self, verbose)
@@ -626,19 +672,20 @@ class Darknet(nn.Module):
         address); call this after editing weights OR BatchNorm buffers through ``.data`` views in place
         (``bn.running_mean.data.zero_()`` moves no version counter: the training engine would pick it up
         only at its next unconditional buffer sync, engine/padded.py push)."""
-        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self._drop_hip_engines()
 
     def _apply(self, fn, *args, **kwargs):
-        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self._drop_hip_engines()
         return super()._apply(fn, *args, **kwargs)
 
     def load_state_dict(self, *args, **kwargs):
-        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self._drop_hip_engines()
         return super().load_state_dict(*args, **kwargs)
 
     def train(self, mode=True):
         if mode:
             self.__dict__['_hip_engine'] = None  # weights are about to change; the train engine re-packs every step
+            self.__dict__['_qat_int8'] = self.__dict__['_qat_quantizers'] = None   # ... and a QAT step may re-calibrate the scales
         return super().train(mode)
 
     def __deepcopy__(self, memo):
@@ -734,7 +781,7 @@ def load_darknet_weights(self, weights, cutoff=-1, pt=False, quant=False, **igno
 
     assert cur.pos == len(cur.flat), 'weights file holds %d floats, model consumed %d' % (len(cur.flat), cur.pos)
     if isinstance(self, Darknet):
-        self.__dict__['_hip_engine'] = self.__dict__['_hip_train_engine'] = None
+        self._drop_hip_engines()
 
 
 def save_weights(self, path='model.weights', cutoff=-1):

@@ -592,6 +592,71 @@ typedef struct yh_eval_match_desc {
 } yh_eval_match_desc;
 int yh_eval_match(const yh_eval_match_desc* d, void* stream);
 
+/* COCO bbox scoring on the device (csrc/cocoeval.hip; the protocol is stated in utils/cocoeval.py, which is also the host path and
+ * the oracle): the greedy matcher of every (image, category) pair in the four area ranges, and the accumulation into the
+ * precision (10, 101, K, 4, 3) / recall (10, K, 4, 3) arrays of doubles.  iouThrs x 10, recThrs x 101, area ranges all / small /
+ * medium / large, maxDets 1 / 10 / 100.  All arithmetic is IEEE fp64, one operation at a time (no contraction, IEEE divide); the
+ * counts are integers and there are no atomics: the outputs are the host statement's bit for bit, and the same bits on every run.
+ * The ordering is the caller's (engine/cocoeval.py, torch.sort(stable=True)):
+ *   dets      DEVICE (n_dets, 4) fp64 x, y, w, h: the detections that count (at most 100 per pair), pair after pair in ascending
+ *             (image, category) order, inside a pair by descending score (stable).  A detection's row number is its SLOT.
+ *   gts       DEVICE (n_gts, 6) fp64 x, y, w, h, area, iscrowd, pair after pair, inside a pair in input order
+ *   pairs     DEVICE (n_pairs, 4) int32: first slot, detections, first ground truth, ground truths of every pair that has either
+ *   iou_thrs  DEVICE 10 fp64; area_rng DEVICE (4, 2) fp64 lo, hi (both bounds belong to the range); rec_thrs DEVICE 101 fp64
+ * yh_coco_match: one workgroup per pair, one wave64 per area range.  The wave walks the pair's detections in order; the ground
+ * truths lie across the lanes (in passes of 64), the IoU row of a detection is computed once for the ten thresholds, and per
+ * threshold the winner is one wave reduction over (not ignored, IoU, ground-truth index): a ground truth that is not ignored beats
+ * every ignored one, then the largest IoU >= min(thr, 1 - 1e-10), then the LATEST index.  A matched ground truth is out of the
+ * running at that threshold unless it is a crowd.  Outputs per area range a:
+ *   dt_matched / dt_ignore  DEVICE (4, n_dets) uint16: bit t = matched / ignored at threshold t (an unmatched detection whose own
+ *                           area w * h lies outside the range is ignored)
+ *   gt_ignore               DEVICE (4, n_gts) uint8: iscrowd or area outside the range
+ *   ws                      DEVICE workspace of yh_coco_workspace(n_dets, n_gts) bytes: the ten matched bits of every (range,
+ *                           ground truth), private to the lane that owns the ground truth
+ * yh_coco_accumulate: one workgroup per (category, area range, maxDets, threshold).  The category's detections are listed by
+ *   cat_dets   DEVICE n_dets int32 slots, category after category, inside a category by descending score with the slot order
+ *              (= image order) as the tie-break (stable); cat_first DEVICE (K + 1) int32 offsets into it
+ *   det_rank   DEVICE n_dets uint8: the rank of a slot inside its pair; a detection of rank >= maxDets counts as neither tp nor fp
+ *   cat_gts    DEVICE n_gts int32 ground-truth rows, category after category; gt_first DEVICE (K + 1) int32
+ * npig = the category's ground truths with gt_ignore == 0; npig == 0 leaves -1 in every entry of the workgroup.  Otherwise one
+ * pass sums tp / fp, a second pass walks the list BACKWARDS in chunks of 256: tp / fp of every element by a workgroup prefix sum,
+ * pr = tp / ((fp + tp) + 2^-52), the running maximum from the end, and every element that is the first to reach a recall
+ * threshold (rc = tp / npig >= r) writes that maximum into precision[t][r][k][a][m]; thresholds never reached get 0; recall[t][k][a][m]
+ * = rc of the last element (0 for an empty list).  pr is never stored: the accumulation needs no workspace.
+ * Null or misaligned arguments, negative counts, K < 1, a workspace that is too small: YH_EINVAL / YH_EALIGN before any launch.
+ * yh_coco_match with n_pairs == 0: YH_OK, nothing is launched.  A pair whose rows do not lie inside dets / gts is skipped.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed. */
+typedef struct yh_coco_match_desc {
+    const double* dets;
+    const double* gts;
+    const int32_t* pairs;
+    const double* iou_thrs;
+    const double* area_rng;
+    uint16_t* dt_matched;
+    uint16_t* dt_ignore;
+    uint8_t* gt_ignore;
+    void* ws;
+    int64_t ws_bytes;
+    int32_t n_pairs, n_dets, n_gts, reserved;
+} yh_coco_match_desc;
+typedef struct yh_coco_accum_desc {
+    const int32_t* cat_dets;
+    const int32_t* cat_first;
+    const uint8_t* det_rank;
+    const int32_t* cat_gts;
+    const int32_t* gt_first;
+    const uint16_t* dt_matched;
+    const uint16_t* dt_ignore;
+    const uint8_t* gt_ignore;
+    const double* rec_thrs;
+    double* precision;
+    double* recall;
+    int32_t n_dets, n_gts, K, reserved;
+} yh_coco_accum_desc;
+int64_t yh_coco_workspace(int64_t n_dets, int64_t n_gts);
+int yh_coco_match(const yh_coco_match_desc* d, void* stream);
+int yh_coco_accumulate(const yh_coco_accum_desc* d, void* stream);
+
 typedef struct yh_wgrad_desc {
     const void* x;          /* forward input of the conv, NHWC dtype (stem: NCHW fp32 image)                    */
     const void* dz;         /* gradient of the conv output, NHWC dtype, pitch lddz                              */

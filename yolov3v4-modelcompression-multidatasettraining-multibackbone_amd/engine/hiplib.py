@@ -218,6 +218,17 @@ class EvalMatchDesc(C.Structure):
                 ('ws_bytes', _i64), ('images', _i32), ('nt', _i32), ('total', _i32), ('niou', _i32), ('width', _f32), ('height', _f32)]
 
 
+class CocoMatchDesc(C.Structure):
+    _fields_ = [('dets', _vp), ('gts', _vp), ('pairs', _vp), ('iou_thrs', _vp), ('area_rng', _vp), ('dt_matched', _vp), ('dt_ignore', _vp),
+                ('gt_ignore', _vp), ('ws', _vp), ('ws_bytes', _i64), ('n_pairs', _i32), ('n_dets', _i32), ('n_gts', _i32), ('reserved', _i32)]
+
+
+class CocoAccumDesc(C.Structure):
+    _fields_ = [('cat_dets', _vp), ('cat_first', _vp), ('det_rank', _vp), ('cat_gts', _vp), ('gt_first', _vp), ('dt_matched', _vp),
+                ('dt_ignore', _vp), ('gt_ignore', _vp), ('rec_thrs', _vp), ('precision', _vp), ('recall', _vp),
+                ('n_dets', _i32), ('n_gts', _i32), ('K', _i32), ('reserved', _i32)]
+
+
 QAT_TRACK_GLOBAL, QAT_TRACK_AVERAGED = 0, 1     # YH_QAT_TRACK_*: the tracker rule of yh_qat_range_update
 EVAL_MATCH_LDS_LABELS = 512     # YH_EVAL_MATCH_LDS_LABELS: labels of one image the kernel stages in LDS (more: its chunked form)
 
@@ -328,6 +339,9 @@ _SIGNATURES = {
     'yh_pack_batch': (C.c_int, [_vp, C.c_int, _vp]),
     'yh_bn_l1_subgrad': (C.c_int, [_vp, C.c_int, C.c_int, _f32, _vp]),
     'yh_eval_match': (C.c_int, [C.POINTER(EvalMatchDesc), _vp]),
+    'yh_coco_workspace': (_i64, [_i64, _i64]),
+    'yh_coco_match': (C.c_int, [C.POINTER(CocoMatchDesc), _vp]),
+    'yh_coco_accumulate': (C.c_int, [C.POINTER(CocoAccumDesc), _vp]),
     'yh_dw_wgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),
     'yh_dw_wgrad_workspace': (_i64, [C.POINTER(DwBwdDesc)]),
     'yh_dw_dgrad': (C.c_int, [C.POINTER(DwBwdDesc), _vp]),

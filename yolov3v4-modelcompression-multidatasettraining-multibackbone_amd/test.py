@@ -5,6 +5,12 @@ prune scripts call ``test(...)[0][2]`` for mAP), fresh code.  On a CUDA device t
 the HIP path (``models.Darknet`` / ``utils.utils.non_max_suppression``), and so does the matching of detections to labels: one launch
 and one host read per batch (``engine.evalmatch.match_batch``; ``YOLO_HIP_EVAL_MATCH=0`` keeps the per-image host loop, which is also
 what CPU tensors run).  AP is host side.
+
+``coco_metrics`` (``--coco-metrics [ANNOTATIONS.json]``) scores the ``results.json`` rows the COCO way - the twelve numbers of
+``COCOeval.summarize``, mAP@[.5:.95] first - without pycocotools: utils/cocoeval.py states the protocol, on a GPU the matching and the
+accumulation run in csrc/cocoeval.hip (engine/cocoeval.py; ``YOLO_HIP_COCO_EVAL=0`` keeps the host statement).  Ground truth is the
+annotation file when one is given, the data set's own label files otherwise.  The result is kept in ``test.coco_result``; the return
+value does not change.
 """
 import argparse
 import glob
@@ -18,8 +24,9 @@ import torch.nn as nn
 from torch.utils.data import DataLoader
 
 from models import Darknet, attempt_download, load_darknet_weights
+from engine import cocoeval as coco_engine
 from engine import evalmatch
-from utils import torch_utils
+from utils import cocoeval, torch_utils
 from utils.datasets import LoadImagesAndLabels, LetterboxBatch
 from utils.parse_config import parse_data_cfg
 from utils.utils import (ap_per_class, box_iou, clip_coords, coco80_to_coco91_class, compute_loss, load_classes,
@@ -30,6 +37,7 @@ try:
 except Exception:  # pragma: no cover
     tqdm = lambda x, **kw: x
 
+coco_result = None   # dict(stats, precision, recall) of the last test(..., coco_metrics=...) call
 opt = None   # set by the CLI below; test() reads it only when it has to build the model itself (reference test.py:32-33)
 
 
@@ -80,7 +88,8 @@ def host_stats(output, targets, height, width, iouv):
 
 def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, iou_thres=0.6, save_json=False, augment=False,
          model=None, dataloader=None, multi_label=True, quantized=-1, a_bit=8, w_bit=8, rank=-1, plot=True, is_gray_scale=False,
-         maxabsscaler=False, shortcut_way=-1):
+         maxabsscaler=False, shortcut_way=-1, coco_metrics=False):
+    global coco_result
     if model is None:
         device = torch_utils.select_device(opt.device if opt is not None else '', batch_size=batch_size)
         verbose = opt is not None and getattr(opt, 'task', 'test') == 'test'
@@ -126,6 +135,9 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
     fused_calls = 0
     loss = torch.zeros(3, device=device)
     jdict, stats, ap, ap_class = [], [], [], []
+    coco_rows = []      # per jdict row (data set index, class): what the label-file ground truth is keyed by
+    coco_shapes = {}    # data set index -> original (h0, w0)
+    coco_index = {f: i for i, f in enumerate(dataloader.dataset.img_files)} if coco_metrics else {}
     for batch_i, (imgs, targets, paths, shapes) in enumerate(tqdm(dataloader, desc=header) if rank in (-1, 0) else dataloader):
         if isinstance(imgs, LetterboxBatch):
             from engine.preprocess import render_letterbox_items
@@ -161,7 +173,9 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
         else:
             stats.extend(host_stats(output, targets, height, width, iouv))
         seen += len(output)
-        for si, pred in enumerate(output if save_json else ()):
+        for si in range(len(output) if coco_metrics else 0):
+            coco_shapes[coco_index[paths[si]]] = tuple(shapes[si][0]) if shapes[si] is not None else tuple(imgs[si].shape[1:])
+        for si, pred in enumerate(output if save_json or coco_metrics else ()):
             if pred is None:
                 continue
             image_id = Path(paths[si]).stem.split('_')[-1]
@@ -175,6 +189,8 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
                 cid = int(row[5])
                 jdict.append({'image_id': image_id, 'category_id': coco91[cid] if cid < len(coco91) else cid,
                               'bbox': [round(x, 3) for x in b], 'score': round(row[4], 5)})
+                if coco_metrics:
+                    coco_rows.append((coco_index[paths[si]], cid))
 
         if batch_i < 1 and plot:
             plot_images(imgs, targets, paths=paths, names=names, fname='test_batch%g_gt.jpg' % batch_i, is_gray_scale=is_gray_scale)
@@ -209,7 +225,23 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
     if save_json and len(jdict):
         with open('results.json', 'w') as f:
             json.dump(jdict, f)
-        print('wrote results.json (%d detections); COCO scoring needs pycocotools, which this image does not ship' % len(jdict))
+        print('wrote results.json (%d detections); --coco-metrics [ANNOTATIONS.json] scores them (mAP@[.5:.95], no pycocotools needed)' % len(jdict))
+    if coco_metrics:
+        dataset = dataloader.dataset
+        if isinstance(coco_metrics, str):       # (a) a COCO annotation file, restricted to the evaluated images
+            gts, image_ids, cat_ids = cocoeval.load_coco_json(coco_metrics, [cocoeval.image_id_of(f) for f in dataset.img_files])
+            dets = cocoeval.dets_from_jdict(jdict, image_ids, cat_ids)
+            n_img, n_cat = len(image_ids), len(cat_ids)
+        else:                                   # (b) the data set's own label files: image id = data set index, categories 0..nc-1
+            seen_idx = sorted(coco_shapes)
+            gts = cocoeval.gts_from_labels([dataset.labels[i] for i in seen_idx], [coco_shapes[i] for i in seen_idx])
+            gts[:, 0] = np.asarray(seen_idx, np.float64)[gts[:, 0].astype(np.int64)] if len(gts) else gts[:, 0]
+            dets = np.asarray([(i, c, *r['bbox'], r['score']) for (i, c), r in zip(coco_rows, jdict)], np.float64).reshape(-1, 7)
+            n_img, n_cat = len(dataset.img_files), nc
+        coco_result = coco_engine.evaluate(dets, gts, n_img, n_cat, device=device)
+        test.coco_result = coco_result
+        if rank in (-1, 0):
+            print('\n'.join(cocoeval.format_stats(coco_result['stats'])))
 
     maps = np.zeros(nc) + map50
     for i, c in enumerate(ap_class):
@@ -229,6 +261,8 @@ if __name__ == '__main__':
     parser.add_argument('--conf-thres', type=float, default=0.001, help='object confidence threshold')
     parser.add_argument('--iou-thres', type=float, default=0.6, help='IOU threshold for NMS')
     parser.add_argument('--save-json', action='store_true', help='save a cocoapi-compatible JSON results file')
+    parser.add_argument('--coco-metrics', nargs='?', const=True, default=False, metavar='ANNOTATIONS.json',
+                        help='print the twelve COCO numbers (mAP@[.5:.95] ...); ground truth: the annotation file, or the label files when none is given')
     parser.add_argument('--task', default='test', help="'test', 'study', 'benchmark'")
     parser.add_argument('--device', default='', help='device id (i.e. 0 or 0,1) or cpu')
     parser.add_argument('--augment', action='store_true', help='augmented inference')
@@ -251,7 +285,7 @@ if __name__ == '__main__':
     if opt.task == 'test':
         test(opt.cfg, opt.data, opt.weights, opt.batch_size, opt.img_size, opt.conf_thres, opt.iou_thres, opt.save_json, opt.augment,
              quantized=opt.quantized, a_bit=opt.a_bit, w_bit=opt.w_bit, is_gray_scale=opt.gray_scale, maxabsscaler=opt.maxabsscaler,
-             shortcut_way=opt.shortcut_way)
+             shortcut_way=opt.shortcut_way, coco_metrics=opt.coco_metrics)
     elif opt.task == 'benchmark':   # mAP / speed over a grid of sizes and NMS thresholds
         rows = []
         for size in (320, 416, 512, 608):

@@ -876,6 +876,17 @@ typedef struct yh_mosaic_desc {
     const uint8_t* lut;          /* [3][256] device table (cv2 arithmetic with hsv != 0)                                   */
 } yh_mosaic_desc;
 int yh_mosaic_affine_hsv(const yh_mosaic_desc* d, void* stream);
+/* A whole batch of items in ONE launch, grid (ceil(out_h * out_w / 256), n): block row y renders item y from dev_descs[y], with the
+ * arithmetic of yh_mosaic_affine_hsv in YH_ARITH_PILLOW operation for operation (both kernels share one per-pixel body).  host_descs
+ * and dev_descs are the same n descriptors in host and in device memory: the caller uploads the table on `stream` before the call
+ * and keeps it alive until the launch has run; the host copy is only validated here - every entry by yh_mosaic_affine_hsv's rules -
+ * and never read by the device.  The table is read through blockIdx.y alone: the fields all lanes share by scalar loads, the four
+ * fields of the part that covers a tap (src, src_pitch, x1b, y1b) per lane, as the single-item kernel does.  src[k] may point anywhere in
+ * device memory (a frame cache: src = arena + offset, src_pitch = frame width * c, (x1b, y1b) = the window's corner), dst is each
+ * item's own [c][out_h][out_w] slot.  YH_EINVAL for n <= 0, n > 65535, a null table, an entry with arith != YH_ARITH_PILLOW, or
+ * entries that differ in out_h, out_w, c, out_dtype or divisor; the validation is host code and launches nothing when it fails.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+int yh_mosaic_affine_hsv_batch(const yh_mosaic_desc* host_descs, const yh_mosaic_desc* dev_descs, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * COS-PTQ calibration on the device.  The scale search every quantiser of the reference runs per calibration batch

@@ -159,11 +159,9 @@ __global__ __launch_bounds__(256) void mosaic_affine_hsv_cv2_kernel(const yh_mos
     store_px<OutT>(d, Y, X, px);
 }
 
+// One output pixel (index i < out_h * out_w) of one item in Pillow's arithmetic: the body both kernels below share.
 template <typename OutT>
-__global__ __launch_bounds__(256) void mosaic_affine_hsv_kernel(const yh_mosaic_desc d) {
-    const long total = (long)d.out_h * d.out_w;
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= total) return;
+__device__ __forceinline__ void mosaic_affine_hsv_pixel(const yh_mosaic_desc& d, long i) {
     const int X = (int)(i % d.out_w), Y = (int)(i / d.out_w);
     const int xo = d.flip_lr ? d.out_w - 1 - X : X;     // the flip mirrors the finished image: output X shows source column W-1-X
     int px[3] = {d.pad_value, d.pad_value, d.pad_value};
@@ -196,10 +194,32 @@ __global__ __launch_bounds__(256) void mosaic_affine_hsv_kernel(const yh_mosaic_
     store_px<OutT>(d, Y, X, px);
 }
 
+template <typename OutT>
+__global__ __launch_bounds__(256) void mosaic_affine_hsv_kernel(const yh_mosaic_desc d) {
+    const long total = (long)d.out_h * d.out_w;
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    mosaic_affine_hsv_pixel<OutT>(d, i);
+}
+
+// A whole batch in one launch: block row blockIdx.y renders item y from descs[y].  The table is read-only for the launch and
+// indexed by blockIdx.y alone, so the fields every lane shares (sizes, inv, gains, the placement rectangles) arrive by scalar loads
+// and the 300-byte struct is never copied per lane.  As in the single-item kernel, which part covers a tap differs from lane to
+// lane, so src[k], src_pitch[k], x1b[k], y1b[k] of that part are per-lane loads (12 dword + 4 dwordx2 in the gfx950 ISA of both
+// kernels); the pixel loads here are flat loads, the frame pointer coming from memory and not from a kernel argument.
+template <typename OutT>
+__global__ __launch_bounds__(256) void mosaic_affine_hsv_batch_kernel(const yh_mosaic_desc* __restrict__ descs) {
+    const yh_mosaic_desc& d = descs[blockIdx.y];
+    const long total = (long)d.out_h * d.out_w;
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    mosaic_affine_hsv_pixel<OutT>(d, i);
+}
+
 }  // namespace yh
 
-extern "C" int yh_mosaic_affine_hsv(const yh_mosaic_desc* d, void* stream) {
-    using namespace yh;
+// What both entries require of one descriptor (host code: reads the descriptor only).
+static int mosaic_desc_valid(const yh_mosaic_desc* d) {
     if (!d || !d->dst) return YH_EINVAL;
     if (d->c != 1 && d->c != 3) return YH_EINVAL;
     if (d->out_h <= 0 || d->out_w <= 0 || d->canvas_h <= 0 || d->canvas_w <= 0 || !(d->divisor > 0.f)) return YH_EINVAL;
@@ -210,12 +230,19 @@ extern "C" int yh_mosaic_affine_hsv(const yh_mosaic_desc* d, void* stream) {
         if (d->x1b[k] < 0 || d->y1b[k] < 0 || d->x1b[k] + (d->x2a[k] - d->x1a[k]) > d->src_w[k] ||
             d->y1b[k] + (d->y2a[k] - d->y1a[k]) > d->src_h[k] || d->src_pitch[k] < d->src_w[k] * d->c) return YH_EINVAL;
     }
+    if (d->arith != YH_ARITH_PILLOW && d->arith != YH_ARITH_CV2_LINEAR) return YH_EINVAL;
+    if (d->arith == YH_ARITH_CV2_LINEAR && d->hsv && d->c == 3 && !d->lut) return YH_EINVAL;
+    if (d->out_dtype != YH_MOSAIC_U8 && d->out_dtype != YH_MOSAIC_F32 && d->out_dtype != YH_MOSAIC_F16) return YH_EINVAL;
+    return YH_OK;
+}
+
+extern "C" int yh_mosaic_affine_hsv(const yh_mosaic_desc* d, void* stream) {
+    using namespace yh;
+    if (mosaic_desc_valid(d) != YH_OK) return YH_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)d->out_h * d->out_w;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (d->arith != YH_ARITH_PILLOW && d->arith != YH_ARITH_CV2_LINEAR) return YH_EINVAL;
     if (d->arith == YH_ARITH_CV2_LINEAR) {
-        if (d->hsv && d->c == 3 && !d->lut) return YH_EINVAL;
         switch (d->out_dtype) {
             case YH_MOSAIC_U8: hipLaunchKernelGGL(mosaic_affine_hsv_cv2_kernel<uint8_t>, dim3(blocks), dim3(256), 0, s, *d); break;
             case YH_MOSAIC_F32: hipLaunchKernelGGL(mosaic_affine_hsv_cv2_kernel<float>, dim3(blocks), dim3(256), 0, s, *d); break;
@@ -228,6 +255,28 @@ extern "C" int yh_mosaic_affine_hsv(const yh_mosaic_desc* d, void* stream) {
         case YH_MOSAIC_U8: hipLaunchKernelGGL(mosaic_affine_hsv_kernel<uint8_t>, dim3(blocks), dim3(256), 0, s, *d); break;
         case YH_MOSAIC_F32: hipLaunchKernelGGL(mosaic_affine_hsv_kernel<float>, dim3(blocks), dim3(256), 0, s, *d); break;
         case YH_MOSAIC_F16: hipLaunchKernelGGL(mosaic_affine_hsv_kernel<f16>, dim3(blocks), dim3(256), 0, s, *d); break;
+        default: return YH_EINVAL;
+    }
+    return check_launch();
+}
+
+extern "C" int yh_mosaic_affine_hsv_batch(const yh_mosaic_desc* host_descs, const yh_mosaic_desc* dev_descs, int n, void* stream) {
+    using namespace yh;
+    if (!host_descs || !dev_descs || n <= 0 || n > 65535) return YH_EINVAL;      // grid.y = n
+    const yh_mosaic_desc& f = host_descs[0];
+    for (int i = 0; i < n; ++i) {
+        const yh_mosaic_desc* d = host_descs + i;
+        if (mosaic_desc_valid(d) != YH_OK || d->arith != YH_ARITH_PILLOW) return YH_EINVAL;
+        if (d->out_h != f.out_h || d->out_w != f.out_w || d->c != f.c || d->out_dtype != f.out_dtype || d->divisor != f.divisor)
+            return YH_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const long total = (long)f.out_h * f.out_w;
+    const dim3 grid((unsigned)((total + 255) / 256), (unsigned)n);
+    switch (f.out_dtype) {
+        case YH_MOSAIC_U8: hipLaunchKernelGGL(mosaic_affine_hsv_batch_kernel<uint8_t>, grid, dim3(256), 0, s, dev_descs); break;
+        case YH_MOSAIC_F32: hipLaunchKernelGGL(mosaic_affine_hsv_batch_kernel<float>, grid, dim3(256), 0, s, dev_descs); break;
+        case YH_MOSAIC_F16: hipLaunchKernelGGL(mosaic_affine_hsv_batch_kernel<f16>, grid, dim3(256), 0, s, dev_descs); break;
         default: return YH_EINVAL;
     }
     return check_launch();

@@ -355,6 +355,7 @@ _SIGNATURES = {
     'yh_yolo_decode_candidates_tta': (C.c_int, [C.POINTER(DecodeDesc), _f32, _f32, _f32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     'yh_tta_deaugment': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32, _f32, _vp]),
     'yh_mosaic_affine_hsv': (C.c_int, [C.POINTER(MosaicDesc), _vp]),
+    'yh_mosaic_affine_hsv_batch': (C.c_int, [C.POINTER(MosaicDesc), _vp, C.c_int, _vp]),
     'yh_ptq_search_workspace': (_i64, [_i64]),
     'yh_ptq_cos_search': (C.c_int, [_vp, _i64, _f32, C.c_int, _f32, _f32, C.c_int, _vp, _i64, _vp, _vp, _vp]),
     'yh_absmax': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),

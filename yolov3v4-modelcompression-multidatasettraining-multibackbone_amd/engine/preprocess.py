@@ -367,6 +367,56 @@ def render_mosaic_items(items, device, out=None, dtype=torch.float32, divisor=25
     return out
 
 
+_MOSAIC_DTYPE = np.dtype(hiplib.MosaicDesc)       # the descriptor as a numpy record: a whole table is filled by columns
+
+
+def render_cached_mosaic_batch(batch, cache, out=None, dtype=torch.float32, divisor=256.0, lib=None):
+    """A ``utils.datasets.CachedMosaicBatch`` (geometry only) -> the network input on the cache's device, read from the frames of
+    ``cache`` (``engine.framecache.DeviceFrameCache``): the values ``render_mosaic_items`` gives for the matching recipes.  Per batch
+    one upload of the ``n`` descriptors (from pinned memory the cache owns; a slot is rewritten only after the event recorded behind
+    its last upload) and ONE ``yh_mosaic_affine_hsv_batch`` launch; no pixel crosses the host.  Pillow arithmetic only."""
+    if lib is None and cache.device.type != 'cuda':
+        raise ValueError('a host arena is rendered by an emulated library only (lib=...): the kernel reads device memory')
+    lib = lib or hiplib.load()
+    n, c = len(batch), batch.channels
+    h, w = batch.out_hw
+    if c != cache.channels:
+        raise ValueError('the batch has %d channels, the cache holds %d' % (c, cache.channels))
+    if batch.index.max() >= len(cache):
+        raise ValueError('the batch names frame %d, the cache holds %d' % (batch.index.max(), len(cache)))
+    code = {torch.uint8: 0, torch.float32: 1, torch.float16: 2}[dtype]
+    device = cache.device
+    if out is None:
+        out = torch.empty((n, c, h, w), device=device, dtype=dtype)
+    assert out.is_contiguous() and tuple(out.shape) == (n, c, h, w) and out.dtype == dtype and out.device == device
+    slot = cache.desc_slot(n)
+    nbytes = n * _MOSAIC_DTYPE.itemsize
+    d = slot.buf.numpy()[:nbytes].view(_MOSAIC_DTYPE)
+    d[:] = np.zeros((), dtype=_MOSAIC_DTYPE)
+    used = batch.index >= 0
+    frame = np.where(used, batch.index, 0)
+    d['src'] = np.where(used, cache.arena.data_ptr() + cache.offsets[frame], 0).astype(np.uint64)
+    d['dst'] = out.data_ptr() + np.arange(n, dtype=np.uint64) * np.uint64(c * h * w * out.element_size())
+    d['inv'], d['hsv_gain'] = batch.inv, batch.hsv_gains
+    d['src_h'], d['src_w'], d['src_pitch'] = batch.hw[:, :, 0], batch.hw[:, :, 1], batch.hw[:, :, 1] * c
+    d['x1a'], d['y1a'], d['x2a'], d['y2a'] = (batch.rect[:, :, q] for q in range(4))
+    d['x1b'], d['y1b'] = batch.window[:, :, 0], batch.window[:, :, 1]
+    d['canvas_h'], d['canvas_w'] = batch.canvas
+    d['out_h'], d['out_w'], d['c'], d['pad_value'] = h, w, c, PAD_VALUE
+    d['hsv'], d['flip_lr'], d['out_dtype'], d['divisor'], d['arith'] = batch.hsv, batch.flip, code, float(divisor), imgtables.ARITH_PILLOW
+    host = C.cast(slot.buf.data_ptr(), C.POINTER(hiplib.MosaicDesc))
+    with hiplib.on_device(out):
+        if device.type == 'cuda':
+            dev = torch.empty(nbytes, dtype=torch.uint8, device=device)     # the caching allocator keeps it for this stream's work
+            dev.copy_(slot.buf[:nbytes], non_blocking=True)
+            cache.release_slot(slot)
+            table = dev.data_ptr()
+        else:
+            table = slot.buf.data_ptr()                                     # a host arena: the emulated library reads host memory
+        hiplib.check(lib.yh_mosaic_affine_hsv_batch(host, table, n, hiplib.stream_ptr()), 'yh_mosaic_affine_hsv_batch')
+    return out
+
+
 _host_cv2_cache = {}
 
 

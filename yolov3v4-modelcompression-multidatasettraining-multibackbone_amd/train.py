@@ -128,6 +128,9 @@ def train(opt, hyp):
     # one process per GPU; the launcher provides the rendezvous (train.py:96-110 hard-codes nccl + tcp://127.0.0.1:9999)
     rank, world = opt.local_rank, int(os.environ.get('WORLD_SIZE', '1'))
     device = torch_utils.select_device(opt.device, batch_size=batch_size)
+    device_cache = bool(getattr(opt, 'device_cache', False))
+    if device_cache and device.type != 'cuda':
+        raise NotImplementedError('--device-cache keeps the training frames in GPU memory and renders them there: it needs a GPU')
     distributed = rank != -1 and world > 1
     if distributed:
         if device.type != 'cpu':
@@ -197,7 +200,17 @@ def train(opt, hyp):
         (not opt.rect or getattr(opt, 'device_augment', False))
     dataset = LoadImagesAndLabels(train_path, img_size, batch_size, augment=True, hyp=hyp, rect=opt.rect, cache_images=opt.cache_images,
                                   rank=rank, is_gray_scale=opt.gray_scale, device_augment=device_augment,
-                                  arith=getattr(opt, 'image_arith', None))
+                                  arith=getattr(opt, 'image_arith', None), device_cache=device_cache)
+    frame_cache = None
+    if device_cache:
+        # every training frame, decoded and resized once, in one arena in device memory (engine/framecache.py): items are geometry
+        # alone and a batch is one yh_mosaic_affine_hsv_batch launch.  Under DDP every rank builds its own full cache - the mosaic
+        # partners of an item are drawn from the whole set
+        from engine.framecache import DeviceFrameCache
+        frame_cache = DeviceFrameCache.build(dataset, device)
+        if _is_main(rank):
+            print('Device frame cache: %d frames, %d bytes on %s, built in %.1f s'
+                  % (len(frame_cache), frame_cache.nbytes, device, frame_cache.build_seconds))
     nw = min([os.cpu_count() or 1, batch_size if batch_size > 1 else 0, 8])
     sampler = torch.utils.data.distributed.DistributedSampler(dataset) if distributed else None
     dataloader = DataLoader(dataset, batch_size=batch_size, num_workers=nw, shuffle=(sampler is None and not opt.rect), sampler=sampler,
@@ -258,7 +271,10 @@ def train(opt, hyp):
             pbar = tqdm(pbar, total=nb)
         for i, (imgs, targets, paths, _) in pbar:
             ni = i + nb * epoch
-            if not torch.is_tensor(imgs):                # recipes (MosaicBatch): rendered on the device, bit-identical to the host items / 256
+            if frame_cache is not None:                  # geometry alone (CachedMosaicBatch): one launch reads the frames from the cache
+                from engine.preprocess import render_cached_mosaic_batch
+                imgs = render_cached_mosaic_batch(imgs, frame_cache, dtype=torch.float32, divisor=256.0)
+            elif not torch.is_tensor(imgs):              # recipes (MosaicBatch): rendered on the device, bit-identical to the host items / 256
                 from engine.preprocess import render_mosaic_items
                 imgs = render_mosaic_items(imgs, device, dtype=torch.float32, divisor=256.0)
             else:
@@ -390,6 +406,9 @@ def make_parser():
     parser.add_argument('--image-arith', choices=['pillow', 'cv2'], default=None,
                         help="uint8 arithmetic of the device input pipeline: 'pillow' = this package's host loader, 'cv2' = the reference's "
                              "OpenCV calls restated (GPU only: needs --device-augment); default: $YOLO_IMAGE_ARITH or pillow")
+    parser.add_argument('--device-cache', action='store_true',
+                        help='keep every training frame, decoded and resized once, in GPU memory and render a batch from it in one '
+                             'launch (needs a GPU and the device-augment path in Pillow arithmetic; every DDP rank holds a full cache)')
     parser.add_argument('--weights', type=str, default='', help='initial weights path')
     parser.add_argument('--t_weights', type=str, default='', help='teacher model weights')
     parser.add_argument('--KDstr', type=int, default=-1, help='KD strategy')
@@ -413,8 +432,21 @@ def make_parser():
     return parser
 
 
+def parse_args(argv=None):
+    """``make_parser().parse_args(argv)`` plus the combinations the parser refuses."""
+    parser = make_parser()
+    opt = parser.parse_args(argv)
+    if opt.device_cache:
+        for flag, on in (('--cache-images', opt.cache_images), ('--host-augment', opt.host_augment), ('--rect', opt.rect),
+                         ('--image-arith cv2', opt.image_arith == 'cv2')):
+            if on:
+                parser.error('--device-cache cannot be combined with %s: it serves the device-augment mosaic path in Pillow '
+                             'arithmetic and is the only cache of the run' % flag)
+    return opt
+
+
 if __name__ == '__main__':
-    opt = make_parser().parse_args()
+    opt = parse_args()
     if opt.resume and not opt.weights:
         opt.weights = last
     for key in ('cfg', 'data'):

@@ -245,17 +245,20 @@ def random_affine(img, targets=(), degrees=10, translate=.1, scale=.1, shear=10,
     return img, affine_targets(targets, M, s, width, height)
 
 
-def mosaic_layout(self, index, is_gray_scale=False, lazy=False):
+def mosaic_layout(self, index, is_gray_scale=False, lazy=False, sizes=None):
     """The random draws and the geometry of ``load_mosaic`` without touching a canvas (datasets.py:553-600): the mosaic centre,
     the three extra image indices, and per image the placement rectangle ``(x1a, y1a, x2a, y2a)`` on the 2s x 2s canvas, the
     matching source corner ``(x1b, y1b)``, the loaded image and its labels in canvas pixels.  ``lazy``: the images stay unresized
-    and every part carries ``(h0, w0, h, w)`` as a fourth entry (the geometry only needs the size after the resize)."""
+    and every part carries ``(h0, w0, h, w)`` as a fourth entry (the geometry only needs the size after the resize).  ``sizes``
+    (the ``(h, w)`` of every resized frame): no file is opened and the frame's index stands where the image would."""
     s = self.img_size
     xc, yc = [int(random.uniform(s * 0.5, s * 1.5)) for _ in range(2)]
     indices = [index] + [random.randint(0, len(self.labels) - 1) for _ in range(3)]
     parts, labels4 = [], []
     for i, idx in enumerate(indices):
-        if lazy:
+        if sizes is not None:
+            img, (h, w) = idx, (int(sizes[idx][0]), int(sizes[idx][1]))
+        elif lazy:
             img, (h0, w0), (h, w), _ = load_image_lazy(self, idx, is_gray_scale)
         else:
             img, _, (h, w) = load_image(self, idx, is_gray_scale)
@@ -336,6 +339,51 @@ class MosaicBatch:
 
     def __len__(self):
         return len(self.items)
+
+
+class CachedMosaicItem:
+    """A ``MosaicItem`` whose frames live in a ``engine.framecache.DeviceFrameCache``: per part ``(frame index, (h, w) of the resized
+    frame, its window (wx0, wy0, wx1, wy1), the placement rectangle (cx0, cy0, cx1, cy1))``, index -1 for a part the warp cannot
+    touch.  Built from the size tables alone (``device_cache``): no image is opened, the random streams are consumed as by
+    ``mosaic_item``."""
+    __slots__ = ('parts', 'canvas', 'out_hw', 'inv', 'hsv_gains', 'flip', 'channels', 'labels', 'path')
+
+
+class CachedMosaicBatch:
+    """A collated batch of ``CachedMosaicItem``: geometry only (a few hundred bytes per item), no pixel."""
+
+    def __init__(self, items):
+        n = len(items)
+        self.canvas, self.out_hw, self.channels = tuple(items[0].canvas), tuple(items[0].out_hw), items[0].channels
+        if any(tuple(it.out_hw) != self.out_hw or tuple(it.canvas) != self.canvas or it.channels != self.channels for it in items):
+            raise ValueError('the items of a batch must share canvas, output size and channels')
+        self.index = np.array([[p[0] for p in it.parts] for it in items], dtype=np.int64).reshape(n, 4)
+        self.hw = np.array([[p[1] for p in it.parts] for it in items], dtype=np.int32).reshape(n, 4, 2)
+        self.window = np.array([[p[2] for p in it.parts] for it in items], dtype=np.int32).reshape(n, 4, 4)
+        self.rect = np.array([[p[3] for p in it.parts] for it in items], dtype=np.int32).reshape(n, 4, 4)
+        self.inv = np.array([it.inv for it in items], dtype=np.float64).reshape(n, 6)
+        self.hsv = np.array([it.hsv_gains is not None for it in items], dtype=np.int32)
+        self.hsv_gains = np.array([[1.0] * 3 if it.hsv_gains is None else it.hsv_gains for it in items], dtype=np.float64).reshape(n, 3)
+        self.flip = np.array([bool(it.flip) for it in items], dtype=np.int32)
+
+    def pin_memory(self):     # nothing to pin: the render writes the descriptors into the cache's own pinned buffer
+        return self
+
+    def __len__(self):
+        return len(self.flip)
+
+
+def frame_size_tables(self):
+    """``(hw0, hw)`` int32 ``(n, 2)``: the decoded and the resized ``(h, w)`` of every frame as ``load_image`` returns them, from the
+    image headers alone.  ``_read`` does not apply the EXIF rotation, so the tables do not either (``exif_size`` would swap them)."""
+    from engine import imgtables
+    hw0, hw = np.zeros((len(self.img_files), 2), dtype=np.int32), np.zeros((len(self.img_files), 2), dtype=np.int32)
+    for i, f in enumerate(self.img_files):
+        with Image.open(f) as im:
+            w0, h0 = im.size
+        hw0[i] = h0, w0
+        hw[i] = imgtables.load_image_plan(h0, w0, self.img_size, self.augment)[0]
+    return hw0, hw
 
 
 def _letterbox_plan(h, w, new_shape, scaleup):
@@ -420,15 +468,17 @@ def letterbox_item(self, index):
     return it
 
 
-def mosaic_item(self, index):
-    """``__getitem__`` of the augmenting mosaic path (datasets.py:470-505) with the image left as a recipe."""
+def mosaic_item(self, index, cached=False):
+    """``__getitem__`` of the augmenting mosaic path (datasets.py:470-505) with the image left as a recipe.  ``cached``: a
+    ``CachedMosaicItem`` - the same draws and geometry from ``self.frame_hw`` alone, frames named by index (``device_cache``)."""
     hyp = self.hyp or {}
     s = self.img_size
-    it = MosaicItem()
+    it = CachedMosaicItem() if cached else MosaicItem()
     it.channels = 1 if self.is_gray_scale else 3
-    it.arith = self.arith
     cv2_arith = self.arith == 'cv2'
-    parts, labels4 = mosaic_layout(self, index, self.is_gray_scale, lazy=cv2_arith)
+    if not cached:
+        it.arith = self.arith
+    parts, labels4 = mosaic_layout(self, index, self.is_gray_scale, lazy=cv2_arith, sizes=self.frame_hw if cached else None)
     M, sc, (width, height) = affine_matrix((2 * s, 2 * s), hyp.get('degrees', 0), hyp.get('translate', 0), hyp.get('scale', 0),
                                            hyp.get('shear', 0), border=-s // 2)
     labels = affine_targets(labels4, M, sc, width, height)
@@ -463,9 +513,15 @@ def mosaic_item(self, index):
         img, (x1a, y1a, x2a, y2a), (x1b, y1b, x2b, y2b) = part[:3]
         cx0, cy0, cx1, cy1 = max(x1a, fx0), max(y1a, fy0), min(x2a, fx1), min(y2a, fy1)
         if cx1 <= cx0 or cy1 <= cy0:
+            if cached:
+                it.parts.append((-1, (0, 0), (0, 0, 0, 0), (0, 0, 0, 0)))
+                continue
             it.parts.append((None, (0, 0, 0, 0), (0, 0)) + ((None,) if cv2_arith else ()))
             continue
         wx0, wy0, wx1, wy1 = x1b + cx0 - x1a, y1b + cy0 - y1a, x1b + cx1 - x1a, y1b + cy1 - y1a    # window of the resized image
+        if cached:        # img is the frame's index here
+            it.parts.append((img, (int(self.frame_hw[img][0]), int(self.frame_hw[img][1])), (wx0, wy0, wx1, wy1), (cx0, cy0, cx1, cy1)))
+            continue
         if not cv2_arith:
             it.parts.append((np.ascontiguousarray(img[wy0:wy1, wx0:wx1]), (cx0, cy0, cx1, cy1), (0, 0)))
             continue
@@ -565,7 +621,7 @@ class LoadImagesAndLabels(Dataset):
 
     def __init__(self, path, img_size=416, batch_size=16, augment=False, hyp=None, rect=False, image_weights=False,
                  cache_images=False, rank=-1, is_gray_scale=False, subset_len=-1, single_cls=False, pad=0.0, device_augment=False,
-                 arith=None, device_letterbox=False):
+                 arith=None, device_letterbox=False, device_cache=False):
         path = str(Path(path))
         if os.path.isdir(path):
             files = sorted(glob.glob(os.path.join(path, '*.*')))
@@ -601,6 +657,14 @@ class LoadImagesAndLabels(Dataset):
                                       "or device_letterbox=True (evaluation); this package's host loader resizes with Pillow")
         if (self.arith == 'cv2' or self.device_letterbox) and cache_images:
             raise NotImplementedError('the device recipes keep the source frames unresized; cache_images is not supported with them')
+        # the resized frames live in device memory (engine/framecache.py DeviceFrameCache, built by the caller from this dataset):
+        # items name them by index and carry geometry only; the mosaic recipe path in Pillow arithmetic, nothing else
+        self.device_cache = bool(device_cache)
+        if self.device_cache:
+            if not self.device_augment or self.arith != 'pillow' or device_letterbox or cache_images:
+                raise NotImplementedError("device_cache serves the mosaic recipes in Pillow arithmetic only: it needs augment=True, "
+                                          "device_augment=True and rect=False, and excludes arith='cv2', device_letterbox and "
+                                          "cache_images (the frames are cached once, on the device)")
         self.is_gray_scale = is_gray_scale
         self.label_files = [x.replace('images', 'labels').replace(os.path.splitext(x)[-1], '.txt') for x in self.img_files]
 
@@ -646,6 +710,8 @@ class LoadImagesAndLabels(Dataset):
             print('Caching labels (%g found, %g missing, %g empty, %g duplicate, for %g images)' % (nf, nm, ne, nd, n))
         assert nf > 0 or n == 0 or not augment, 'No labels found in %s. See %s' % (os.path.dirname(self.label_files[0]), help_url)
 
+        if self.device_cache:       # image headers only: what __getitem__ and DeviceFrameCache.build size everything from
+            self.frame_hw0, self.frame_hw = frame_size_tables(self)
         if cache_images:
             self.img_hw0, self.img_hw = [None] * n, [None] * n
             for i in range(n):
@@ -659,7 +725,7 @@ class LoadImagesAndLabels(Dataset):
             index = self.indices[index]
         hyp = self.hyp or {}
         if self.device_augment:
-            return mosaic_item(self, index)
+            return mosaic_item(self, index, cached=self.device_cache)
         if self.device_rect_augment:
             return rect_train_item(self, index)
         if self.device_letterbox:
@@ -708,6 +774,11 @@ class LoadImagesAndLabels(Dataset):
             for i, it in enumerate(batch):
                 it.labels[:, 0] = i
             return MosaicBatch(batch), torch.cat([it.labels for it in batch], 0), tuple(it.path for it in batch), (None,) * len(batch)
+        if batch and isinstance(batch[0], CachedMosaicItem):   # device_cache: (CachedMosaicBatch, labels, paths, shapes)
+            for i, it in enumerate(batch):
+                it.labels[:, 0] = i
+            return (CachedMosaicBatch(batch), torch.cat([it.labels for it in batch], 0), tuple(it.path for it in batch),
+                    (None,) * len(batch))
         if batch and isinstance(batch[0], LetterboxItem):  # device_letterbox: (LetterboxBatch, labels, paths, shapes)
             for i, it in enumerate(batch):
                 it.labels[:, 0] = i

@@ -539,6 +539,32 @@ typedef struct yh_bn_l1_row {
 } yh_bn_l1_row;
 int yh_bn_l1_subgrad(const yh_bn_l1_row* rows, int first, int last, float s, void* stream);
 
+/* Model EMA (csrc/ema.hip): the exponential moving average of a whole state_dict in ONE launch.  Replaces the per-tensor loop of
+ * `ModelEMA.update` (utils/torch_utils.py: `v.mul_(d).add_(src[k], alpha=1 - d)` on every floating-point tensor, two launches each,
+ * 732 on YOLOv3) and reads ema and src once instead of ema twice.
+ *   rows      DEVICE array of n_rows rows, 8-byte aligned.  ema / src are dense fp32 of n >= 1 elements at any 4-byte alignment (a row
+ *             whose two addresses are both 16-byte aligned moves as 16-byte loads and stores, its last n % 4 elements and every other
+ *             row one float at a time: nothing is read or written past n on either side).  A row's ema may overlap no other row's ema
+ *             or src.  Rows are cut into chunks of YH_EMA_CHUNK elements; chunk0 is the index of the row's first chunk, the sum of
+ *             ceil(n_j / YH_EMA_CHUNK) over the rows before it (strictly increasing, rows[0].chunk0 == 0)
+ *   n_chunks  the same sum over all rows (>= n_rows); the grid is min(n_chunks, 2048) workgroups of 256 threads that stride over the
+ *             chunks, each finding its row by binary search over chunk0
+ *   d, one_minus_d   the decay and its complement, each rounded ONCE from the caller's double to fp32
+ * For every element: t = fl32(ema[i] * d); ema[i] = fma(one_minus_d, src[i], t) - one fused multiply-add, the bits of
+ * `v.mul_(d).add_(src, alpha=1 - d)` as torch evaluates it on the device (and on the CPU); NaN, infinities, signed zeros and
+ * denormals follow IEEE-754 as they do there.  No atomics, no LDS, no workspace: the same bits on every run.
+ * n_rows == 0: YH_OK, nothing is launched.  A null table, negative counts, n_chunks < n_rows: YH_EINVAL; a table address that is not
+ * 8-byte aligned: YH_EALIGN; both before any launch.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+#define YH_EMA_CHUNK 4096            /* elements of one row that one workgroup pass serves */
+typedef struct yh_ema_row {
+    float* ema;             /* destination: the averaged tensor, dense fp32                                     */
+    const float* src;       /* the live tensor, same element count                                              */
+    int64_t n;              /* elements, >= 1                                                                   */
+    int64_t chunk0;         /* index of this row's first chunk                                                  */
+} yh_ema_row;
+int yh_ema_update(const yh_ema_row* rows, int n_rows, int64_t n_chunks, float d, float one_minus_d, void* stream);
+
 /* Evaluation statistics of one batch (csrc/evalmatch.hip): which detections are true positives - the per-image loop of the mAP
  * protocol (reference test.py:139-185: clip_coords, per label class two nonzero calls, a box_iou and one host read per
  * over-threshold detection) as ONE launch, one workgroup of 256 threads per image.  For image b with detections pred (n, 6)

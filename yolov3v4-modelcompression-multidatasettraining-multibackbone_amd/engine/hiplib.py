@@ -209,6 +209,13 @@ class BnL1Row(C.Structure):
     _fields_ = [('gamma', _vp), ('grad', _vp), ('n', _i32), ('reserved', _i32)]
 
 
+class EmaRow(C.Structure):
+    _fields_ = [('ema', _vp), ('src', _vp), ('n', _i64), ('chunk0', _i64)]
+
+
+EMA_CHUNK = 4096     # YH_EMA_CHUNK: elements of one row that one workgroup pass of yh_ema_update serves
+
+
 class EvalMatchRow(C.Structure):
     _fields_ = [('pred', _vp), ('n', _i32), ('out_off', _i32), ('lab_first', _i32), ('nl', _i32)]
 
@@ -338,6 +345,7 @@ _SIGNATURES = {
     'yh_maxpool2d_bwd': (C.c_int, [C.POINTER(PoolBwdDesc), _vp]),
     'yh_pack_batch': (C.c_int, [_vp, C.c_int, _vp]),
     'yh_bn_l1_subgrad': (C.c_int, [_vp, C.c_int, C.c_int, _f32, _vp]),
+    'yh_ema_update': (C.c_int, [_vp, C.c_int, _i64, _f32, _f32, _vp]),
     'yh_eval_match': (C.c_int, [C.POINTER(EvalMatchDesc), _vp]),
     'yh_coco_workspace': (_i64, [_i64, _i64]),
     'yh_coco_match': (C.c_int, [C.POINTER(CocoMatchDesc), _vp]),

@@ -112,7 +112,11 @@ def scale_img(img, ratio=1.0, same_shape=True):
 
 
 class ModelEMA:
-    """Exponential moving average of a model's state_dict with a ramped decay."""
+    """Exponential moving average of a model's state_dict with a ramped decay.
+
+    On a GPU the whole update is one ``yh_ema_update`` launch over a device table of the floating-point tensors (engine/ema.py;
+    the bits of the torch statement below, which tensors that do not qualify keep); ``YOLO_HIP_EMA=0`` keeps the per-tensor torch
+    loop there too, for A/B runs.  CPU models take the torch loop."""
 
     def __init__(self, model, decay=0.9999, device=''):
         self.ema = deepcopy(model)
@@ -120,6 +124,7 @@ class ModelEMA:
         self.updates = 0
         self.decay = lambda n: decay * (1 - math.exp(-n / 2000))
         self.device = device
+        self._hip = None    # engine.ema.EmaState: the device row table, built on the first GPU update
         if device:
             self.ema.to(device=device)
         for p in self.ema.parameters():
@@ -132,6 +137,12 @@ class ModelEMA:
         with torch.no_grad():
             src = (model.module if wrapped else model).state_dict()
             dst = (self.ema.module if wrapped else self.ema).state_dict()
+            from engine import ema as hip_ema  # HIP path; raises on a GPU if the library is missing
+            if hip_ema.enabled(dst):
+                if self._hip is None:
+                    self._hip = hip_ema.EmaState()
+                self._hip.update(dst, src, d)
+                return
             for k, v in dst.items():
                 if v.dtype.is_floating_point:
                     v.mul_(d).add_(src[k].detach(), alpha=1. - d)

@@ -471,6 +471,21 @@ typedef struct yh_loss_desc {
 } yh_loss_desc;
 int yh_yolo_loss_fwd(const yh_loss_desc* d, void* stream);
 int yh_yolo_loss_bwd(const yh_loss_desc* d, void* stream);
+/* The same loss with hyp['fl_gamma'] > 0: the reference wraps both BCEs in FocalLoss (utils/utils.py FocalLoss, the TF-addons form,
+ * alpha = 0.25 as compute_loss constructs it) and keeps their mean reduction.  Same descriptor, same launches, same sums / count /
+ * tobj contract; only the element of lobj and lcls changes.  With s = sigmoid(x), B = BCE(x, t) (pos_weight included):
+ *   q = t + s * (1 - 2 t)  (= 1 - p_t),   a = t * alpha + (1 - t) * (1 - alpha),   M = q^gamma
+ *   L = B * a * M
+ *   dL/dx = a * (dB/dx * M + B * gamma * q^(gamma - 1) * (1 - 2 t) * s * (1 - s))
+ * t is soft (tobj is GIoU-valued, cp / cn for the classes).  Where q <= 0 - s rounded to t in fp32: a logit beyond about +-17 on
+ * the side of its 0 / 1 target - L and dL/dx are 0, the limit (B vanishes like q).  That is a deliberate difference from
+ * fp32 torch: its 1 - p_t drops the low bits of s, and for gamma < 1 its autograd returns inf / nan; these entries compute the value
+ * of the formula and stay finite.  The box term, the target assignment and the normalisation are yh_yolo_loss_fwd / _bwd's.
+ * gamma must be finite and > 0, alpha finite and in [0, 1]: YH_EINVAL otherwise and for everything yh_yolo_loss_fwd / _bwd
+ * refuse, before any launch.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+int yh_yolo_loss_focal_fwd(const yh_loss_desc* d, float gamma, float alpha, void* stream);
+int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float alpha, void* stream);
 
 /* Backward of the depthwise block and of squeeze-excite (training of the Mobilenet / Ghost backbones).
  *  yh_dw_wgrad   dw[c][r][s] += sum_pixels dz[p][c] * x[p shifted by (r, s)][c]   (fp32 [c][k][k], caller zeroes)

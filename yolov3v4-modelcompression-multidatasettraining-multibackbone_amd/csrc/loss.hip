@@ -1,5 +1,7 @@
 // compute_loss of the reference (utils/utils.py:368-432) and its hand-derived gradient, fused: a handful of launches per
 // head instead of ~200 small torch kernels and several full-size zero-filled temporaries in autograd.
+#include <cmath>
+
 #include "common.h"
 
 namespace yh {
@@ -42,6 +44,31 @@ __device__ __forceinline__ float bce(float x, float t, float pw) {
 __device__ __forceinline__ float bce_grad(float x, float t, float pw) {
     const float s = sigmoidf(x);
     return s * (1.f - t + pw * t) - pw * t;
+}
+
+// One BCE element of the class / objectness terms, optionally under FocalLoss (utils/utils.py FocalLoss, the alpha-balanced TF-addons
+// form the reference wraps around both BCEs when hyp['fl_gamma'] > 0):  L = B * a * q^gamma,  q = 1 - p_t = t + s * (1 - 2 t),
+// a = t * alpha + (1 - t) * (1 - alpha).  FOCAL == false is the plain BCE, the code of the default loss.  Where q <= 0 (s rounded to
+// t in fp32) value and derivative are 0, the limit: B vanishes like q.  A NaN logit fails `q <= 0` and propagates, as in the BCE.
+template <bool FOCAL>
+__device__ __forceinline__ float loss_elem(float x, float t, float pw, float gamma, float alpha) {
+    const float B = bce(x, t, pw);
+    if constexpr (!FOCAL) return B;
+    const float q = t + sigmoidf(x) * (1.f - 2.f * t);
+    const float a = t * alpha + (1.f - t) * (1.f - alpha);
+    return q <= 0.f ? 0.f : B * a * powf(q, gamma);
+}
+// dL/dx = a * (bce_grad * M + B * gamma * q^(gamma - 1) * (1 - 2 t) * s * (1 - s)),  M = q^gamma.  One pow: q^(gamma - 1) = M / q, taken
+// as (B / q) * M - B / q stays O(1) (B ~ q where q is small), M / q alone overflows for gamma < 1 at the smallest q.
+template <bool FOCAL>
+__device__ __forceinline__ float loss_elem_grad(float x, float t, float pw, float gamma, float alpha) {
+    if constexpr (!FOCAL) return bce_grad(x, t, pw);
+    const float s = sigmoidf(x), u = 1.f - 2.f * t;
+    const float q = t + s * u;
+    if (q <= 0.f) return 0.f;
+    const float a = t * alpha + (1.f - t) * (1.f - alpha);
+    const float M = powf(q, gamma);
+    return a * (bce_grad(x, t, pw) * M + (bce(x, t, pw) / q) * M * gamma * u * s * (1.f - s));
 }
 
 // GIoU of the predicted box (from 4 raw logits, xywh) against the target (xywh), bbox_iou(x1y1x2y2=False, GIoU=True)
@@ -119,7 +146,8 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const yh_loss_desc d) 
 // matched candidates, forward: box and class sums, objectness targets.  One thread per (candidate, class) - the class loop of a
 // candidate used to run inside one thread (80 dependent global loads + BCEs: 33 - 83 us for 1536 threads, latency bound); the thread
 // of class 0 also takes the box term.  nc == 1: one thread per candidate, no class term (as the reference, utils.py:412).
-__global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_desc d) {
+template <bool FOCAL>
+__global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = idx / ncl, c = idx - k * ncl;
@@ -133,14 +161,15 @@ __global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_des
             lbox = 1.f - g.v;
             if (d.winner[m.cell] == k) d.tobj[m.cell] = (1.f - d.gr) + d.gr * fmaxf(g.v, 0.f);
         }
-        if (d.nc > 1) lcls = bce(ps[5 + c], c == m.cls ? d.cp : d.cn, d.cls_pw);
+        if (d.nc > 1) lcls = loss_elem<FOCAL>(ps[5 + c], c == m.cls ? d.cp : d.cn, d.cls_pw, gamma, alpha);
     }
     block_sum_atomic(lbox, d.sums + 0);
     if (d.nc > 1) block_sum_atomic(lcls, d.sums + 2);
 }
 
 // every cell, forward: objectness BCE against tobj (32-bit cell decode: the launcher keeps the cell count below 2^31)
-__global__ __launch_bounds__(256) void loss_obj_fwd_kernel(const yh_loss_desc d) {
+template <bool FOCAL>
+__global__ __launch_bounds__(256) void loss_obj_fwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const unsigned cells = (unsigned)d.bs * d.na * d.ny * d.nx;
     float acc = 0.f;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += gridDim.x * blockDim.x) {
@@ -149,7 +178,7 @@ __global__ __launch_bounds__(256) void loss_obj_fwd_kernel(const yh_loss_desc d)
         const unsigned y = r % (unsigned)d.ny;
         r /= (unsigned)d.ny;
         const unsigned a = r % (unsigned)d.na, b = r / (unsigned)d.na;
-        acc += bce(d.p[(long)b * d.sb + (long)a * d.sa + (long)y * d.sy + (long)x * d.sx + 4], d.tobj[i], d.obj_pw);
+        acc += loss_elem<FOCAL>(d.p[(long)b * d.sb + (long)a * d.sa + (long)y * d.sy + (long)x * d.sx + 4], d.tobj[i], d.obj_pw, gamma, alpha);
     }
     block_sum_atomic(acc, d.sums + 1);
 }
@@ -158,10 +187,45 @@ __global__ __launch_bounds__(256) void loss_obj_fwd_kernel(const yh_loss_desc d)
 // values of one grid position (contiguous in the NHWC head tensors: consecutive threads store consecutive floats), the position
 // decoded once per row with 32-bit arithmetic.  (The first form decoded every ELEMENT with five 64-bit divisions: 0.41 ms for the
 // 76 x 76 head of YOLOv3-608 batch 64 - 1 TB/s - against 0.1 ms of bytes.)
-__global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc d) {
+template <bool FOCAL>
+__global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const int row = d.na * d.no;                              // any width: a thread takes elements j, j + 256, .. of the row
     const int pixels = d.bs * d.ny * d.nx, hw = d.ny * d.nx;
     const float sc = *d.scale * d.g_obj / (float)((long)d.bs * d.na * d.ny * d.nx);
+    if constexpr (FOCAL) {
+        // The focal derivative is a few hundred instructions (exp, log1p, pow, divisions) and only the na objectness slots of a row
+        // need it: inside the row loop below a whole wave executes them for ONE live lane, and the kernel is bound by that issue
+        // (0.87 ms against the plain kernel's 0.35 ms on the three heads of YOLOv3-608 batch 64).  So the workgroup first evaluates
+        // the slots of up to 256 / na of its pixels with one lane each and parks them in LDS; the row loop then only stores.
+        const int per = 256 / d.na;                           // pixels per pass; na > 256: 0, the loop below serves such a head
+        if (per > 0) {
+            __shared__ float gobj[256];
+            const int kk = threadIdx.x / d.na, ka = threadIdx.x - kk * d.na;
+            for (long p0 = blockIdx.x; p0 < pixels; p0 += (long)per * gridDim.x) {      // workgroup-uniform trip count
+                const long ps = p0 + (long)kk * gridDim.x;                 // the pixel whose slot ka this lane stages
+                if (kk < per && ps < pixels) {
+                    const int b = (int)ps / hw, r = (int)ps - b * hw;     // ps < pixels < 2^31: 32-bit decode
+                    const int y = r / d.nx, x = r - y * d.nx;
+                    const long cell = (((long)b * d.na + ka) * d.ny + y) * d.nx + x;
+                    gobj[threadIdx.x] = sc * loss_elem_grad<true>(d.p[(long)b * d.sb + (long)ka * d.sa + (long)y * d.sy + (long)x * d.sx + 4],
+                                                                  d.tobj[cell], d.obj_pw, gamma, alpha);
+                }
+                __syncthreads();
+                for (int j = threadIdx.x; j < row; j += 256) {
+                    const int a = j / d.no, o = j - a * d.no;
+                    for (int k = 0; k < per; ++k) {
+                        const long p = p0 + (long)k * gridDim.x;
+                        if (p >= pixels) break;
+                        const int b = (int)p / hw, r = (int)p - b * hw;
+                        const int y = r / d.nx, x = r - y * d.nx;
+                        d.grad[(long)b * d.gb + (long)a * d.ga + (long)y * d.gy + (long)x * d.gx + o] = o == 4 ? gobj[k * d.na + a] : 0.f;
+                    }
+                }
+                __syncthreads();
+            }
+            return;
+        }
+    }
     for (int j = threadIdx.x; j < row; j += 256) {            // one trip for na * no <= 256 (COCO: 255), more for nc > 80
         const int a = j / d.no, o = j - a * d.no;
         for (int p = blockIdx.x; p < pixels; p += gridDim.x) {
@@ -170,7 +234,8 @@ __global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc 
             float g = 0.f;
             if (o == 4) {
                 const long cell = (((long)b * d.na + a) * d.ny + y) * d.nx + x;
-                g = sc * bce_grad(d.p[(long)b * d.sb + (long)a * d.sa + (long)y * d.sy + (long)x * d.sx + 4], d.tobj[cell], d.obj_pw);
+                g = sc * loss_elem_grad<FOCAL>(d.p[(long)b * d.sb + (long)a * d.sa + (long)y * d.sy + (long)x * d.sx + 4], d.tobj[cell], d.obj_pw, gamma,
+                                               alpha);
             }
             d.grad[(long)b * d.gb + (long)a * d.ga + (long)y * d.gy + (long)x * d.gx + o] = g;
         }
@@ -179,7 +244,8 @@ __global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc 
 
 // matched candidates, backward: box and class terms added on top of the dense pass (duplicates of a cell accumulate); one thread per
 // (candidate, class) as in the forward
-__global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_desc d) {
+template <bool FOCAL>
+__global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = idx / ncl, c = idx - k * ncl;
@@ -197,7 +263,7 @@ __global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_des
     }
     if (d.nc > 1) {
         const float w_cls = *d.scale * d.g_cls / (float)((long)nb * d.nc);
-        atomicAdd(gp + 5 + c, w_cls * bce_grad(ps[5 + c], c == m.cls ? d.cp : d.cn, d.cls_pw));
+        atomicAdd(gp + 5 + c, w_cls * loss_elem_grad<FOCAL>(ps[5 + c], c == m.cls ? d.cp : d.cn, d.cls_pw, gamma, alpha));
     }
 }
 
@@ -213,6 +279,36 @@ static inline unsigned grid_n(long total) {
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// FocalLoss parameters of the yh_yolo_loss_focal_* entries: gamma finite and > 0, alpha finite and in [0, 1]
+static int check_focal(float gamma, float alpha) {
+    if (!std::isfinite(gamma) || !(gamma > 0.f) || !std::isfinite(alpha) || alpha < 0.f || alpha > 1.f) return YH_EINVAL;
+    return YH_OK;
+}
+
+template <bool FOCAL>
+static int loss_fwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
+    if (d->nt > 0) {
+        const unsigned blocks = (unsigned)(((long)d->na * d->nt + 255) / 256);
+        const unsigned cblocks = (unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256);
+        hipLaunchKernelGGL(loss_assign_kernel, dim3(blocks), dim3(256), 0, s, *d);
+        hipLaunchKernelGGL((loss_matched_fwd_kernel<FOCAL>), dim3(cblocks), dim3(256), 0, s, *d, gamma, alpha);
+    }
+    if ((long)d->bs * d->na * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
+    hipLaunchKernelGGL((loss_obj_fwd_kernel<FOCAL>), dim3(grid_n((long)d->bs * d->na * d->ny * d->nx)), dim3(256), 0, s, *d, gamma, alpha);
+    return check_launch();
+}
+
+template <bool FOCAL>
+static int loss_bwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
+    if ((long)d->bs * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
+    const long pixels = (long)d->bs * d->ny * d->nx;
+    hipLaunchKernelGGL((loss_dense_bwd_kernel<FOCAL>), dim3((unsigned)(pixels < 16384 ? pixels : 16384)), dim3(256), 0, s, *d, gamma, alpha);
+    if (d->nt > 0)
+        hipLaunchKernelGGL((loss_matched_bwd_kernel<FOCAL>), dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)),
+                           dim3(256), 0, s, *d, gamma, alpha);
+    return check_launch();
+}
+
 }  // namespace yh
 
 using namespace yh;
@@ -220,27 +316,25 @@ using namespace yh;
 extern "C" int yh_yolo_loss_fwd(const yh_loss_desc* d, void* stream) {
     int rc = check_loss(d, false);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (d->nt > 0) {
-        const unsigned blocks = (unsigned)(((long)d->na * d->nt + 255) / 256);
-        const unsigned cblocks = (unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256);
-        hipLaunchKernelGGL(loss_assign_kernel, dim3(blocks), dim3(256), 0, s, *d);
-        hipLaunchKernelGGL(loss_matched_fwd_kernel, dim3(cblocks), dim3(256), 0, s, *d);
-    }
-    if ((long)d->bs * d->na * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
-    hipLaunchKernelGGL(loss_obj_fwd_kernel, dim3(grid_n((long)d->bs * d->na * d->ny * d->nx)), dim3(256), 0, s, *d);
-    return check_launch();
+    return loss_fwd<false>(d, 0.f, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int yh_yolo_loss_bwd(const yh_loss_desc* d, void* stream) {
     int rc = check_loss(d, true);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((long)d->bs * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
-    const long pixels = (long)d->bs * d->ny * d->nx;
-    hipLaunchKernelGGL(loss_dense_bwd_kernel, dim3((unsigned)(pixels < 16384 ? pixels : 16384)), dim3(256), 0, s, *d);
-    if (d->nt > 0)
-        hipLaunchKernelGGL(loss_matched_bwd_kernel, dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)), dim3(256), 0,
-                           s, *d);
-    return check_launch();
+    return loss_bwd<false>(d, 0.f, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int yh_yolo_loss_focal_fwd(const yh_loss_desc* d, float gamma, float alpha, void* stream) {
+    int rc = check_loss(d, false);
+    if (!rc) rc = check_focal(gamma, alpha);
+    if (rc) return rc;
+    return loss_fwd<true>(d, gamma, alpha, (hipStream_t)stream);
+}
+
+extern "C" int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float alpha, void* stream) {
+    int rc = check_loss(d, true);
+    if (!rc) rc = check_focal(gamma, alpha);
+    if (rc) return rc;
+    return loss_bwd<true>(d, gamma, alpha, (hipStream_t)stream);
 }

@@ -10,8 +10,15 @@ backward while the forward still runs.
 The reference's label check (``build_targets`` asserts every class < nc, utils.py:757-760) needs the labels on the host;
 here the kernels record a label error mask on the device, the mask is copied to pinned host memory asynchronously and the
 same AssertionError is raised by the NEXT ``compute_loss`` call (or ``flush_label_check()``), after the copy has landed.
+
+``hyp['fl_gamma'] > 0`` (the reference wraps both BCEs in ``FocalLoss(gamma, alpha=0.25)``) takes the same node through the focal
+entries ``yh_yolo_loss_focal_fwd`` / ``_bwd``: the same launches with the focal element in the objectness and class terms, the same
+sums, counts, normalisation and label check.  ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for focal loss (A/B runs);
+``stats()`` counts the focal calls.  Where a logit is saturated on the side of its 0 / 1 target the kernels return the limit 0 and
+stay finite; fp32 torch returns inf / nan there for gamma < 1 (include/yolo_hip.h).
 """
 import ctypes as C
+import os
 
 import torch
 
@@ -19,17 +26,30 @@ from . import hiplib
 from .hiplib import LossDesc
 
 _LIB_OVERRIDE = None   # tests inject the host emulation here
+FOCAL_ALPHA = 0.25     # utils.utils.compute_loss builds FocalLoss(bce, fl_gamma) with the class's default alpha
+_STATS = dict(focal_fwd=0, focal_bwd=0)
 
 
 def _lib():
     return _LIB_OVERRIDE if _LIB_OVERRIDE is not None else hiplib.load()
 
 
+def stats():
+    """Counters since ``reset_stats``: calls of the focal forward and backward entries (one per head and pass)."""
+    return dict(_STATS)
+
+
+def reset_stats():
+    for k in _STATS:
+        _STATS[k] = 0
+
+
 def usable(p, model):
-    """Fused path: CUDA (or an injected emulator), fp32 raw heads with unit stride on the last axis, no focal loss."""
+    """Fused path: CUDA (or an injected emulator), fp32 raw heads with unit stride on the last axis; focal loss too unless
+    ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for it."""
     if _LIB_OVERRIDE is None and not p[0].is_cuda:
         return False
-    if model.hyp.get('fl_gamma', 0.0) > 0:
+    if model.hyp.get('fl_gamma', 0.0) > 0 and os.environ.get('YOLO_HIP_FOCAL_LOSS', '1') == '0':
         return False
     return all(t.dtype == torch.float32 and t.dim() == 5 and t.stride(4) == 1 for t in p)
 
@@ -99,7 +119,11 @@ class _YoloLoss(torch.autograd.Function):
                          bs=bs, na=na, ny=ny, nx=nx, no=no, nc=no - 5, nt=nt, iou_t=meta['iou_t'], gr=meta['gr'],
                          cp=meta['cp'], cn=meta['cn'], cls_pw=meta['cls_pw'], obj_pw=meta['obj_pw'],
                          g_box=meta['giou'], g_obj=meta['obj'], g_cls=meta['cls'])
-            hiplib.check(lib.yh_yolo_loss_fwd(C.byref(d), hiplib.stream_ptr()), 'yh_yolo_loss_fwd')
+            if meta['gamma'] > 0:
+                hiplib.check(lib.yh_yolo_loss_focal_fwd(C.byref(d), meta['gamma'], meta['alpha'], hiplib.stream_ptr()), 'yh_yolo_loss_focal_fwd')
+                _STATS['focal_fwd'] += 1
+            else:
+                hiplib.check(lib.yh_yolo_loss_fwd(C.byref(d), hiplib.stream_ptr()), 'yh_yolo_loss_fwd')
             heads.append((d, tobj, p))
             cells.append(float(bs * na * ny * nx))
             del winner   # only the forward needs it (stream-ordered free)
@@ -118,6 +142,7 @@ class _YoloLoss(torch.autograd.Function):
             _pending.append((None, counts, nc))
             flush_label_check()
         ctx.heads, ctx.keep_fwd = heads, (targets, counts, meta['anchors'])
+        ctx.focal = (meta['gamma'], meta['alpha'])
         loss = lbox + lobj + lcls
         ctx.mark_non_differentiable(lbox, lobj, lcls)
         return loss, lbox, lobj, lcls
@@ -127,6 +152,7 @@ class _YoloLoss(torch.autograd.Function):
     def backward(ctx, g_loss, g_lbox, g_lobj, g_lcls):
         lib = _lib()
         scale = g_loss.detach().float().contiguous().reshape(1)
+        gamma, alpha = ctx.focal
         grads = []
         for d, tobj, p in ctx.heads:
             if ctx.on_bases:
@@ -141,7 +167,11 @@ class _YoloLoss(torch.autograd.Function):
             d.grad, d.scale = hiplib.ptr(g), hiplib.ptr(scale)
             d.gb, d.ga, d.gy, d.gx = g.stride(0), g.stride(1), g.stride(2), g.stride(3)
             with hiplib.on_device(p):
-                hiplib.check(lib.yh_yolo_loss_bwd(C.byref(d), hiplib.stream_ptr()), 'yh_yolo_loss_bwd')
+                if gamma > 0:
+                    hiplib.check(lib.yh_yolo_loss_focal_bwd(C.byref(d), gamma, alpha, hiplib.stream_ptr()), 'yh_yolo_loss_focal_bwd')
+                    _STATS['focal_bwd'] += 1
+                else:
+                    hiplib.check(lib.yh_yolo_loss_bwd(C.byref(d), hiplib.stream_ptr()), 'yh_yolo_loss_bwd')
             grads.append(full)
         ctx.keep = scale
         return (None,) + tuple(grads)
@@ -156,7 +186,8 @@ def compute_loss(p, targets, model, yolo_modules, smooth_bce):
     anchors = [layer.anchor_vec.to(device=dev, dtype=torch.float32).contiguous() for layer in yolo_modules(model)]
     meta = dict(targets=targets.to(device=dev, dtype=torch.float32).contiguous(), anchors=anchors, iou_t=float(h['iou_t']),
                 gr=float(model.gr), cp=float(cp), cn=float(cn), cls_pw=float(h['cls_pw']),
-                obj_pw=float(h['obj_pw']), giou=float(h['giou']), obj=float(h['obj']), cls=float(h['cls']))
+                obj_pw=float(h['obj_pw']), giou=float(h['giou']), obj=float(h['obj']), cls=float(h['cls']),
+                gamma=float(h.get('fl_gamma', 0.0)), alpha=FOCAL_ALPHA)
     bases = _head_bases(p)
     with hiplib.on_device(p[0]):
         if bases is not None:

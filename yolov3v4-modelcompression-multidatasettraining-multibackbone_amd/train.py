@@ -124,6 +124,10 @@ def train(opt, hyp):
     train_path, test_path, nc = data_dict['train'], data_dict['valid'], int(data_dict['classes'])
     hyp = dict(hyp)
     hyp['cls'] *= nc / 80
+    if getattr(opt, 'fl_gamma', None) is not None:
+        hyp['fl_gamma'] = opt.fl_gamma
+    if hyp['fl_gamma'] and _is_main(opt.local_rank):
+        print('Using FocalLoss(gamma=%g)' % hyp['fl_gamma'])      # reference train.py:52-53
 
     # one process per GPU; the launcher provides the rendezvous (train.py:96-110 hard-codes nccl + tcp://127.0.0.1:9999)
     rank, world = opt.local_rank, int(os.environ.get('WORLD_SIZE', '1'))
@@ -385,6 +389,14 @@ def train(opt, hyp):
     return results
 
 
+def _focal_gamma(text):
+    """--fl-gamma: a finite float >= 0."""
+    v = float(text)
+    if not math.isfinite(v) or v < 0:
+        raise argparse.ArgumentTypeError('must be a finite number >= 0, got %r' % text)
+    return v
+
+
 def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--epochs', type=int, default=300)
@@ -416,6 +428,9 @@ def make_parser():
     parser.add_argument('--device', default='', help='device id (i.e. 0 or 0,1 or cpu)')
     parser.add_argument('--adam', action='store_true', help='use adam optimizer')
     parser.add_argument('--ema', action='store_true', help='use ema')
+    parser.add_argument('--fl-gamma', type=_focal_gamma, default=None,
+                        help="focal loss gamma (0: plain BCE); default: the hyp dict's fl_gamma.  On a GPU the fused loss kernels "
+                             'carry it (YOLO_HIP_FOCAL_LOSS=0 keeps the torch statement)')
     parser.add_argument('--pretrain', '-pt', dest='pt', action='store_true', help='load the whole darknet weights file')
     parser.add_argument('--mixedprecision', '-mpt', dest='mpt', action='store_true', help='mixed precision training')
     parser.add_argument('--s', type=float, default=0.001, help='scale sparse rate')

@@ -238,9 +238,9 @@ def compute_loss(p, targets, model, fused=None):
     """GIoU box loss + objectness BCE + class BCE over the raw head tensors (reference utils.py:368-432).
 
     Returns ``(loss, detached [lbox, lobj, lcls, loss])``; mean reduction, gains from ``model.hyp``, objectness
-    target ``(1 - gr) + gr * giou`` with ``model.gr``.  CUDA fp32 raw heads without focal loss go through the fused HIP
-    kernels (engine/loss.py, csrc/loss.hip: same values, gradient written directly); everything else runs the torch
-    ops below."""
+    target ``(1 - gr) + gr * giou`` with ``model.gr``.  CUDA fp32 raw heads go through the fused HIP kernels, with
+    ``hyp['fl_gamma'] > 0`` through their focal form (engine/loss.py, csrc/loss.hip: same values, gradient written
+    directly); everything else runs the torch ops below."""
     if fused is not False and (p[0].is_cuda or _fused_loss_override()):
         from engine import loss as hip_loss
         if hip_loss.usable(p, model):

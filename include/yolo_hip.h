@@ -580,6 +580,55 @@ typedef struct yh_ema_row {
 } yh_ema_row;
 int yh_ema_update(const yh_ema_row* rows, int n_rows, int64_t n_chunks, float d, float one_minus_d, void* stream);
 
+/* Attention-transfer distillation (csrc/kd.hip): the feature term of the reference's compute_lost_KD4 (utils/utils.py:553-563) reads a
+ * conv block's output only through A = feature.abs().sum(1), one fp32 number per pixel.  Three entries take the maps where the engines'
+ * NHWC activations are, evaluate KLDivLoss(sum)(log_softmax(A_s / T), softmax(A_t / T)) * T * T / batch over all features, and put the
+ * loss's gradient back into the training engine's NHWC gradient buffers.  No float atomics anywhere: the same bits on every run.
+ *
+ * yh_kd_row: one feature.  Pixel q = n * hw + p of the feature is the `c` channels at y + (q * ld + c_off) elements (NHWC, row pitch
+ * ld); its map value lives at out[out_off + q], its gradient row at dy + (q * ld + c_off) elements (same dtype and geometry as y; only
+ * yh_kd_inject reads dy, yh_kd_attention accepts NULL).  c, ld and c_off are multiples of 8 and y / dy are 16-byte aligned (YH_EALIGN
+ * is the caller's to avoid: the table is device memory, the library cannot read it).  Rows are cut into chunks of YH_KD_CHUNK pixels;
+ * chunk0 is the index of a row's first chunk (rows[0].chunk0 == 0, strictly increasing), n_chunks the sum over all rows.
+ *
+ * yh_kd_attention: out[out_off + q] = sum_c |y[q, c]| in fp32.  A pixel of fewer than 64 channels is summed by one lane, channel 0
+ * upwards; otherwise by 8 lanes (lane j takes the 8-channel groups j, j + 8, ...) combined by a fixed butterfly: the order depends on c
+ * alone.  Pad lanes that hold zeros add nothing.
+ *
+ * yh_kd_attention_kl: kl rows (DEVICE array of yh_kd_kl_row) are the (feature, image) rows of both maps, a_s and a_t in one layout.
+ * One workgroup of YH_KD_KL_THREADS threads per row, three sweeps: the maxima, the two sums of exp((a - max) / T), then
+ * p_s, p_t, G[off + i] = p_s - p_t and the row's sum of p_t * (log p_t - log p_s) (0 where p_t underflows to 0, as torch.xlogy).  Row
+ * partials go to `partials` (n_rows floats); a finishing launch of one workgroup adds them in a fixed order and stores
+ * loss[0] = sum * T * T / batch.  The gradient of loss[0] with respect to a_s is (T / batch) * G.
+ *
+ * yh_kd_inject: for every feature row, pixel and channel: dy = round_to_dtype(float(dy) + t * sign(y)) with
+ * t = fl32(fl32(g[0] * coef) * G[out_off + q]) and sign(0) = 0 (torch's abs backward); g is a DEVICE fp32 scalar (the upstream gradient,
+ * e.g. the GradScaler scale), coef = T / batch rounded once to fp32.  Channels outside [c_off, c_off + c) are not touched.
+ *
+ * n_rows == 0: YH_OK, nothing is launched.  Null pointers, negative counts, n_chunks < n_rows, T <= 0, batch <= 0: YH_EINVAL; a
+ * table that is not 8-byte aligned: YH_EALIGN; both before any launch.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+#define YH_KD_CHUNK 256              /* pixels of one feature that one workgroup pass of yh_kd_attention / yh_kd_inject serves */
+#define YH_KD_KL_THREADS 1024        /* elements of one row that one workgroup pass of yh_kd_attention_kl serves */
+typedef struct yh_kd_row {
+    const void* y;          /* the feature's buffer, NHWC, YH_F16 or YH_F32                                     */
+    void* dy;               /* its gradient buffer, same dtype / pitch / channel offset (yh_kd_inject)          */
+    int64_t out_off;        /* first element of the feature's map in the flat map buffer                        */
+    int64_t chunk0;         /* index of this row's first chunk                                                  */
+    int32_t dtype;          /* YH_F16 / YH_F32                                                                  */
+    int32_t n, hw;          /* images, pixels per image                                                         */
+    int32_t c, ld, c_off;   /* physical channels, row pitch, first channel (elements)                           */
+} yh_kd_row;
+typedef struct yh_kd_kl_row {
+    int64_t off;            /* first element of the row in a_s, a_t and G                                       */
+    int32_t len;            /* elements, >= 1                                                                   */
+    int32_t reserved;       /* 0                                                                                */
+} yh_kd_kl_row;
+int yh_kd_attention(const yh_kd_row* rows, int n_rows, int64_t n_chunks, float* out, void* stream);
+int yh_kd_attention_kl(const float* a_s, const float* a_t, float* G, const yh_kd_kl_row* rows, int n_rows, float* partials, float* loss,
+                       float T, int batch, void* stream);
+int yh_kd_inject(const yh_kd_row* rows, int n_rows, int64_t n_chunks, const float* G, const float* g, float coef, void* stream);
+
 /* Evaluation statistics of one batch (csrc/evalmatch.hip): which detections are true positives - the per-image loop of the mAP
  * protocol (reference test.py:139-185: clip_coords, per label class two nonzero calls, a box_iou and one host read per
  * over-threshold detection) as ONE launch, one workgroup of 256 threads per image.  For image b with detections pred (n, 6)

@@ -216,6 +216,19 @@ class EmaRow(C.Structure):
 EMA_CHUNK = 4096     # YH_EMA_CHUNK: elements of one row that one workgroup pass of yh_ema_update serves
 
 
+class KdRow(C.Structure):
+    _fields_ = [('y', _vp), ('dy', _vp), ('out_off', _i64), ('chunk0', _i64), ('dtype', _i32), ('n', _i32), ('hw', _i32), ('c', _i32),
+                ('ld', _i32), ('c_off', _i32)]
+
+
+class KdKlRow(C.Structure):
+    _fields_ = [('off', _i64), ('len', _i32), ('reserved', _i32)]
+
+
+KD_CHUNK = 256       # YH_KD_CHUNK: pixels of one feature that one workgroup pass of yh_kd_attention / yh_kd_inject serves
+KD_KL_THREADS = 1024  # YH_KD_KL_THREADS: elements of one row that one workgroup pass of yh_kd_attention_kl serves
+
+
 class EvalMatchRow(C.Structure):
     _fields_ = [('pred', _vp), ('n', _i32), ('out_off', _i32), ('lab_first', _i32), ('nl', _i32)]
 
@@ -346,6 +359,9 @@ _SIGNATURES = {
     'yh_pack_batch': (C.c_int, [_vp, C.c_int, _vp]),
     'yh_bn_l1_subgrad': (C.c_int, [_vp, C.c_int, C.c_int, _f32, _vp]),
     'yh_ema_update': (C.c_int, [_vp, C.c_int, _i64, _f32, _f32, _vp]),
+    'yh_kd_attention': (C.c_int, [_vp, C.c_int, _i64, _vp, _vp]),
+    'yh_kd_attention_kl': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _f32, C.c_int, _vp]),
+    'yh_kd_inject': (C.c_int, [_vp, C.c_int, _i64, _vp, _vp, _f32, _vp]),
     'yh_eval_match': (C.c_int, [C.POINTER(EvalMatchDesc), _vp]),
     'yh_coco_workspace': (_i64, [_i64, _i64]),
     'yh_coco_match': (C.c_int, [C.POINTER(CocoMatchDesc), _vp]),

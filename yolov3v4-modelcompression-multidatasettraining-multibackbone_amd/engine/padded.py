@@ -329,6 +329,14 @@ class PaddedTrainEngine:
     lib = property(lambda self: self.inner.lib)
 
     _arena = property(lambda self: self.inner._arena)
+    step_maps = property(lambda self: self.inner.step_maps)
+
+    # attention steps (engine/kd.py): the twin has the model's blocks one for one, and a pad lane holds y = 0 exactly - it adds
+    # nothing to sum_c |y|, and sign(0) = 0 keeps its gradient an exact zero under the injection
+    attention = property(lambda self: self.inner.attention, lambda self, on: setattr(self.inner, 'attention', on))
+
+    def attention_maps(self, flat):
+        return self.inner.attention_maps(flat)
 
     def _get_plan(self, x):
         return self.inner._get_plan(x)
@@ -361,9 +369,9 @@ class PaddedTrainEngine:
         self.pad.pull_stats()
         return heads
 
-    def backward_segment(self, k, head_grads):
+    def backward_segment(self, k, head_grads, maps_grad=None):
         plan = self.inner._current
-        twin_grads = self.inner.backward_segment(k, head_grads)
+        twin_grads = self.inner.backward_segment(k, head_grads, maps_grad)
         real_subset = self.segment_parameters(plan)[k]
         return self.pad.map_grads(real_subset, twin_grads)
 

@@ -896,7 +896,10 @@ class DarknetEngine:
             for k in range(len(plan['raw_shapes'])):
                 lib.yh_plan_bind_slot(handle, SLOT_RAW0 + k, raws[k].data_ptr() if raws else hiplib.SLOT_NULL)
             hiplib.check(lib.yh_plan_run(handle, hiplib.stream_ptr()), 'yh_plan_run')
-        feats = self._features(plan) if self.return_features else []
+        if self.return_features == 'attention':
+            feats = self._attention(plan)
+        else:
+            feats = self._features(plan) if self.return_features else []
         return io, tuple(raws), feats
 
     def detect(self, x, conf_thres=0.3, iou_thres=0.6, multi_label=False, classes=None, agnostic=False, augment=False):
@@ -1128,6 +1131,29 @@ class DarknetEngine:
                     mods[i + 1].__class__.__name__ != 'YOLOLayer':
                 feats.append(self.block_output(plan, i))
         return feats
+
+    def _attention(self, plan):
+        """``return_features == 'attention'``: sum_c |y| of the same blocks as an ``AttentionMaps`` (engine/kd.py) - (N, H, W) fp32
+        views of one fresh flat buffer, written by ONE launch straight from the plan's NHWC activations.  No NCHW copy is made.
+        Pad lanes of a padded tensor hold zeros (zero weight rows, zero bias, every activation maps 0 to 0) and add nothing."""
+        from . import kd
+        if self.q:
+            raise NotImplementedError('attention maps are taken from a float graph (fp16 / fp32 activations)')
+        table = plan.get('kd_table')
+        if table is None:
+            mods, feats = self.model.module_list, []
+            for i, m in enumerate(mods):
+                if m.__class__.__name__ == 'Sequential' and i + 1 < len(mods) and mods[i + 1].__class__.__name__ != 'YOLOLayer':
+                    v = plan['outs'][i]
+                    if v is None or v.kind == 'input' or v.storage is None or v.fp32:
+                        raise NotImplementedError('HIP engine: block %d has no activation buffer to take an attention map from' % i)
+                    feats.append(dict(y=v.storage.data_ptr(), dy=None, dtype=self.code, n=plan['N'], h=v.H, w=v.W, c=v.c_phys, ld=v.ld,
+                                      c_off=v.c_off))
+            raw, plan['kd_rows'], plan['kd_chunks'], plan['kd_shapes'] = kd.feature_rows(feats)
+            table = plan['kd_table'] = kd.to_device(raw, self.device)
+        flat = torch.empty(sum(n * h * w for n, h, w in plan['kd_shapes']), device=self.device, dtype=torch.float32)
+        kd.run_attention(table, plan['kd_rows'], plan['kd_chunks'], flat, self.lib)
+        return kd.AttentionMaps(flat, plan['kd_shapes'])
 
     def block_output(self, plan, i):
         """Output of cfg block ``i`` as an NCHW fp32 tensor (debug / feature_out); None if fused away."""

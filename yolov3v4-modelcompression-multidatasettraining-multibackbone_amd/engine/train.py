@@ -183,6 +183,11 @@ class TrainEngine(DarknetEngine):
         self.steps = 0   # forward count; the autograd node checks it so a stale backward fails loudly
         self._l1_blocks = ()   # network-slimming sparsity: blocks whose BatchNorm gamma carries the L1 penalty (set_bn_sparsity)
         self._l1_s = 0.0
+        # feature distillation (engine/kd.py): steps whose plans also write the attention maps sum_c |y| of every conv block the
+        # reference lists in feature_out, and take the gradient of a loss on them (models.Darknet.hip_return_features = 'attention')
+        self.attention = False
+        self.step_maps = None
+        self._building_attention = False
 
     # --------------------------------------------------------------------------------- parameters
     def parameters(self):
@@ -345,7 +350,30 @@ class TrainEngine(DarknetEngine):
                 if v.bn is not None and v.fp32:
                     raise NotImplementedError('HIP training path: BatchNorm on a yolo-head conv')
 
-    def _build_train_plan(self, N, Cin, H, W):
+    def _build_train_plan(self, N, Cin, H, W, attention=False):
+        # attention plans are built like the evaluation engine's feature_out plans: every conv block keeps its own output (no
+        # shortcut / upsample fused into its store), and the next block's data gradient is never folded into the first block's
+        # one-pass backward (that form does not materialise the gradient the injection lands in)
+        self.return_features = self._building_attention = bool(attention)
+        try:
+            return self._build_train_plan_(N, Cin, H, W, bool(attention))
+        finally:
+            self.return_features = self._building_attention = False
+
+    def _attention_values(self, outs):
+        """The values whose maps are taken: the blocks ``DarknetEngine._features`` selects (a Sequential not followed by a yolo layer)."""
+        mods, feats = self.model.module_list, []
+        for i, m in enumerate(mods):
+            if m.__class__.__name__ == 'Sequential' and i + 1 < len(mods) and mods[i + 1].__class__.__name__ != 'YOLOLayer':
+                v = outs[i]
+                if v is None or v.kind == 'input' or v.fp32:
+                    raise NotImplementedError('HIP training path: block %d has no activation buffer to take an attention map from' % i)
+                feats.append(v)
+        if not feats:
+            raise NotImplementedError('HIP training path: the graph has no feature_out block')
+        return feats
+
+    def _build_train_plan_(self, N, Cin, H, W, attention):
         values, heads, outs = self._build_values(N, Cin, H, W)
         self._check_supported(values)
         self._place(values)
@@ -702,6 +730,18 @@ class TrainEngine(DarknetEngine):
         # ---- pass 3: backward ops.  A gradient storage's first writer must cover it entirely; otherwise the
         # storage is zeroed before the backward plan runs and every contribution accumulates.
         initialised = set()
+        if attention:
+            # Feature distillation injects into the gradient of every feature value BEFORE the first backward op runs (one place:
+            # backward_segment of the last range).  So these buffers start as zeros and every contribution accumulates - also the
+            # ones that would otherwise have been the first, full-width write; a concat buffer one of them is produced into is zeroed
+            # as a whole, and the injection touches that value's lanes only.  The fusions that take a block's BatchNorm backward sums
+            # while completing its dy (completes_bn_block) stay on: they reduce the values they STORE, residual accumulate
+            # included, and the injection is already part of what they accumulate onto.
+            feats = plan['kd_values'] = self._attention_values(outs)
+            for u in feats:
+                if id(u.gstorage) not in initialised:
+                    initialised.add(id(u.gstorage))
+                    plan['zero_list'].append(u.gstorage)
         # gradient buffers addressed by more than one value (a concat and the parts produced into it, a tensor and its channel
         # slices): the residual-gradient aliasing below re-points ONE value's buffer and must leave these alone
         holders = {}
@@ -1006,6 +1046,20 @@ class TrainEngine(DarknetEngine):
                 emit_wgrad()
         plan['head_shapes'] = [(N, h.src.H, h.src.W, h.src.c_phys) for h in heads]
         plan['segments'] = self._make_segments(plan, values, heads, bwd_pos)
+        if attention:
+            # maps, G = p_s - p_t and the KL row partials are pieces of the step arena like every other step buffer: a reservation
+            # over all shapes covers them (train_stats' arena_bytes), the two tables are the plan's own (plan_bytes)
+            from . import kd
+            total = sum(N * u.H * u.W for u in feats)
+            sink = plan['kd_sink'] = kd.KdSink()
+            sink.lib = self.lib
+            raw, sink.n_kl_rows = kd.kl_rows([(N, u.H, u.W) for u in feats])
+            plan['kd_maps'], plan['kd_G'] = alloc((total,), fp32=True), alloc((total,), fp32=True)
+            plan['kd_partials'] = alloc((max(sink.n_kl_rows, 4),), fp32=True)
+            sink.kl_table = keep(len(raw), torch.uint8)
+            sink.kl_table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            plan['kd_table'] = keep(len(feats) * C.sizeof(hiplib.KdRow), torch.uint8, zero=True)
+            plan['kd_one'] = keep(1, torch.float32, zero=True).fill_(1.0)
         plan['ws'] = alloc((max(plan['ws_floats'], 4),), fp32=True)
         plan['ws2'] = alloc((max(plan['ws2_floats'], 4),), fp32=True)
         if async_reduce:
@@ -1037,6 +1091,15 @@ class TrainEngine(DarknetEngine):
             lib.yh_plan_bind_slot(handle, SLOT_WS, base + plan['ws'].off)
         lib.yh_plan_bind_slot(plan['bwd'], SLOT_WS2, base + plan['ws2'].off)
         plan['bound'] = base
+        if plan.get('kd_values'):
+            # the row table of the attention / inject launches holds addresses: rewritten whenever the arena moved
+            from . import kd
+            esz = plan['kd_values'][0].storage.element_size()
+            raw, plan['kd_rows'], plan['kd_chunks'], plan['kd_shapes'] = kd.feature_rows(
+                [dict(y=base + u.storage.off, dy=base + u.gstorage.off, dtype=self.code, n=plan['N'], h=u.H, w=u.W, c=u.c_phys, ld=u.ld,
+                      c_off=u.c_off) for u in plan['kd_values']])
+            assert all((base + u.storage.off) % 16 == 0 and (u.c_off * esz) % 16 == 0 for u in plan['kd_values'])
+            plan['kd_table'].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
 
     def _stem_bwd_fused(self, v, s):
         """The one-pass backward of the first block applies: fp16 step, 3x3 / stride 1 / pad 1 on a 1- or 3-channel image, 16 or
@@ -1052,6 +1115,8 @@ class TrainEngine(DarknetEngine):
         (YOLO_HIP_STEM_DGRAD=0 keeps it a launch of its own)."""
         s = v.src
         if os.environ.get('YOLO_HIP_STEM_DGRAD', '1') == '0' or os.environ.get('YOLO_HIP_WGRAD_LANE', '0') == '1':
+            return False
+        if self._building_attention:      # the first block's dy takes an injection: it has to exist as a buffer
             return False
         if v.kind != 'conv' or s.kind != 'conv' or s.src.kind != 'input' or not self._stem_bwd_fused(s, s.src):
             return False
@@ -1084,7 +1149,13 @@ class TrainEngine(DarknetEngine):
             self.device = x.device
         elif self.device != x.device:
             raise RuntimeError('engine was built on %s, input is on %s' % (self.device, x.device))
-        return self._plan_for(tuple(x.shape))
+        return self._plan_for(self._plan_key(x.shape))
+
+    def _plan_key(self, shape):
+        """Plans are keyed by the input shape; the plans of attention steps (other ops, other buffers) carry the flag on top, so
+        the plain plan of a shape is the same object, with the same ops, whether or not attention steps run in between."""
+        key = tuple(int(k) for k in shape)
+        return key + (True,) if self.attention else key
 
     def _cached_plan(self, key):
         """The plan of input shape ``key``, built on first use.  Plans hold descriptors and small per-shape state; the step buffers
@@ -1125,7 +1196,7 @@ class TrainEngine(DarknetEngine):
             raise ValueError('reserve() takes (N, C, H, W) shapes')
         if self.device is None:
             self.device = next(self.model.parameters()).device
-        self._ensure_arena(max([self._cached_plan(key)['arena_need'] for key in shapes] + [self._arena.capacity]))
+        self._ensure_arena(max([self._cached_plan(self._plan_key(key))['arena_need'] for key in shapes] + [self._arena.capacity]))
 
     def train_stats(self):
         plans = list(self._tplans.values())
@@ -1149,6 +1220,16 @@ class TrainEngine(DarknetEngine):
         for k, h in enumerate(heads):
             lib.yh_plan_bind_slot(plan['fwd'], SLOT_HEAD0 + k, h.data_ptr())
         hiplib.check(lib.yh_plan_run(plan['fwd'], hiplib.stream_ptr()), 'yh_plan_run(train forward)')
+        self.step_maps = None
+        if plan.get('kd_values'):
+            # one launch after the forward plan: the maps of every feature, out of the activations where they lie
+            from . import kd
+            sink = plan['kd_sink']
+            self.step_maps = self._arena.view(plan['kd_maps'].off, plan['kd_maps'].n, torch.float32)
+            sink.G = self._arena.view(plan['kd_G'].off, plan['kd_G'].n, torch.float32)
+            sink.partials = self._arena.view(plan['kd_partials'].off, plan['kd_partials'].n, torch.float32)
+            sink.pending = None
+            kd.run_attention(plan['kd_table'], plan['kd_rows'], plan['kd_chunks'], self.step_maps, self.lib)
         counters = [v.bn.num_batches_tracked for v in plan['values']
                     if v.kind == 'conv' and v.bn is not None and v.bn.num_batches_tracked is not None]
         if counters:
@@ -1188,9 +1269,34 @@ class TrainEngine(DarknetEngine):
         assert segs[0]['ops'][1] == len(plan['bwd_ops']) and segs[-1]['ops'][0] == 0
         return segs
 
-    def backward_segment(self, k, head_grads):
+    def attention_maps(self, flat):
+        """The step's ``AttentionMaps`` over ``flat`` - the autograd output that aliases ``step_maps``."""
+        from . import kd
+        plan = self._current
+        return kd.AttentionMaps(flat, plan['kd_shapes'], sink=plan['kd_sink'])
+
+    def _inject_feature_grads(self, plan, maps_grad):
+        """The ONE place where the gradient of a loss on the attention maps enters: after the gradient buffers were zeroed, before
+        the first backward op.  The fused KL node left (g, coef, G) in the plan's sink; a torch statement on the maps arrives as an
+        ordinary gradient of the flat buffer and takes the same launch with g = 1."""
+        from . import kd
+        sink = plan['kd_sink']
+        pending, sink.pending = sink.pending, None
+        if pending is not None:
+            g, coef, G = pending
+            plan['bwd_keep'] += [g, G]
+            kd.run_inject(plan['kd_table'], plan['kd_rows'], plan['kd_chunks'], G, g, coef, self.lib)
+        if maps_grad is not None:
+            G = maps_grad.contiguous().float()
+            if G.numel() != plan['kd_maps'].n:
+                raise ValueError('gradient of the attention maps has %d elements, expected %d' % (G.numel(), plan['kd_maps'].n))
+            plan['bwd_keep'].append(G)
+            kd.run_inject(plan['kd_table'], plan['kd_rows'], plan['kd_chunks'], G, plan['kd_one'], 1.0, self.lib)
+
+    def backward_segment(self, k, head_grads, maps_grad=None):
         """Run backward range ``k`` (the last range first).  ``head_grads``: fp32 gradients of this range's heads, in the
-        order of ``plan['segments'][k]['heads']``.  Returns the fp32 gradients of the range's parameters."""
+        order of ``plan['segments'][k]['heads']``; ``maps_grad`` (last range of an attention step only): the gradient of the flat
+        attention-map buffer, if autograd produced one.  Returns the fp32 gradients of the range's parameters."""
         plan = self._current
         if plan is None:
             raise RuntimeError('backward() without a preceding forward()')
@@ -1203,6 +1309,8 @@ class TrainEngine(DarknetEngine):
             lib.yh_plan_bind_slot(plan['bwd'], SLOT_INPUT, x.data_ptr())
             plan['bwd_next'] = nseg - 1
             plan['bwd_keep'] = []
+            if plan.get('kd_values'):
+                self._inject_feature_grads(plan, maps_grad)
         if plan.get('bwd_next') != k:
             raise RuntimeError('backward ranges must run last to first (expected %s, got %d)' % (plan.get('bwd_next'), k))
         for j, g in zip(seg['heads'], head_grads):

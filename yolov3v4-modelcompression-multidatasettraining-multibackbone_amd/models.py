@@ -349,6 +349,12 @@ class _HipTrainSegment(torch.autograd.Function):
         plan = engine._current
         ctx.engine, ctx.k, ctx.step = engine, k, engine.steps
         heads = [engine.step_heads[j] for j in plan['segments'][k]['heads']]
+        # an attention step (engine/kd.py): the flat buffer of the maps leaves through the LAST range's node, the first to run in
+        # backward - whatever a loss on the maps sends back is there before any backward range has run
+        ctx.maps = engine.step_maps is not None and k == len(plan['segments']) - 1
+        if ctx.maps:
+            ctx.set_materialize_grads(False)
+            heads.append(engine.step_maps)
         return (torch.zeros(1, device=heads[0].device if heads else engine.step_heads[0].device),) + tuple(heads)
 
     @staticmethod
@@ -359,7 +365,10 @@ class _HipTrainSegment(torch.autograd.Function):
             raise RuntimeError('HIP training path: backward() of a forward whose buffers were overwritten by a later '
                                'forward (one forward per backward, like gradient checkpointing-free eager training)')
         with _on_device(eng.device):
-            grads = eng.backward_segment(ctx.k, head_grads)
+            if ctx.maps:
+                grads = eng.backward_segment(ctx.k, head_grads[:-1], head_grads[-1])
+            else:
+                grads = eng.backward_segment(ctx.k, head_grads)
         return (None, None, None) + tuple(grads)
 
 
@@ -404,8 +413,9 @@ class Darknet(nn.Module):
         self.hip_precision = os.environ.get('YOLO_HIP_PRECISION', 'fp16')
         # feature_out (models.py:540-543: every conv block not feeding a yolo layer, used by the feature-distillation
         # losses KD4 / KD5) costs an NCHW fp32 copy of ~70 tensors per forward, so the HIP paths return [] unless asked:
-        # eval copies them out of the engine's buffers; the training step does not carry them (the feature-distillation
-        # strategies are out of scope) and raises when asked
+        # True: eval copies them out of the engine's buffers; the training step does not carry them and raises when asked.
+        # 'attention': both engines return an engine.kd.AttentionMaps instead - abs().sum(1) of each of those tensors, all that
+        # compute_lost_KD4 reads of them, as (N, H, W) fp32 views of one flat buffer written by one launch
         self.hip_return_features = False
         if quantized == -1:
             self.info(verbose)
@@ -478,9 +488,11 @@ class Darknet(nn.Module):
         # cannot lower raises - there is no eager fallback and no switch that selects one (tests that want the eager modules
         # on a GPU call `_forward_eager` themselves).
         use = x.is_cuda and self.training and self.quantized == -1
-        if use and self.__dict__.get('hip_return_features', False):
-            raise NotImplementedError('feature_out is not produced by the HIP training step: the feature-distillation losses '
-                                      '(reference train.py KDstr 2-5) are out of scope; clear hip_return_features')
+        want = self.__dict__.get('hip_return_features', False)
+        if use and want and want != 'attention':
+            raise NotImplementedError("the HIP training step does not hand out feature_out (NCHW fp32 copies of every conv block): "
+                                      "set hip_return_features = 'attention' for the channel-summed maps compute_lost_KD4 reads "
+                                      "(engine/kd.py), or clear it")
         return use
 
     def forward_once(self, x, augment=False, verbose=False):
@@ -505,6 +517,8 @@ class Darknet(nn.Module):
             eng = make_train_engine(self, precision, x)
             self.__dict__['_hip_train_engine'] = eng
         eng.set_bn_sparsity(*self.__dict__.get('_hip_bn_sparsity', (None, 0.0)))   # survives engine rebuilds: the setting lives here
+        attention = self.__dict__.get('hip_return_features', False) == 'attention'
+        eng.attention = attention           # attention steps have plans of their own (keyed by the flag): the plain plan is untouched
         plan = eng._get_plan(x)
         heads = [None] * len(self.yolo_layers)
         token = x
@@ -513,12 +527,13 @@ class Darknet(nn.Module):
             token = res[0]
             for j, h in zip(plan['segments'][k]['heads'], res[1:]):
                 heads[j] = h
+        feature_out = eng.attention_maps(res[-1]) if attention else []
         yolo_out = []
         for h, idx in zip(heads, self.yolo_layers):
             m = self.module_list[idx]
             bs, ny, nx, _ = h.shape
             yolo_out.append(h[..., :m.na * m.no].view(bs, ny, nx, m.na, m.no).permute(0, 3, 1, 2, 4))
-        return yolo_out, []
+        return yolo_out, feature_out
 
     def hip_set_bn_sparsity(self, prune_idx, s):
         """Network-slimming sparse training on the HIP step: the L1 subgradient ``s * sign(gamma)`` of the BatchNorm gammas of the
@@ -548,6 +563,7 @@ class Darknet(nn.Module):
             if eng is None or eng.precision != precision:
                 eng = make_train_engine(self, precision, max(shapes, key=lambda s: s[0] * s[2] * s[3]))
                 self.__dict__['_hip_train_engine'] = eng
+            eng.attention = self.__dict__.get('hip_return_features', False) == 'attention'    # reserve the plans the steps will run
             eng.reserve(shapes)
 
     def hip_train_stats(self):
@@ -566,7 +582,8 @@ class Darknet(nn.Module):
         if eng is None or eng.precision != precision:
             eng = DarknetEngine(self, precision=precision)
             self.__dict__['_hip_engine'] = eng
-        eng.return_features = bool(self.__dict__.get('hip_return_features', False))
+        want = self.__dict__.get('hip_return_features', False)
+        eng.return_features = 'attention' if want == 'attention' else bool(want)     # 'attention': engine/kd.py AttentionMaps
         # the second return value - the raw (bs, na, ny, nx, no) head maps, models.py:336-340 - is a copy the engine makes only for
         # callers that read it (test.py's validation loss); detect.py reads model(img)[0] alone and switches it off
         eng.want_raw = bool(self.__dict__.get('hip_return_raw', True))

@@ -32,7 +32,7 @@ ALLOW = {
 
 def kernels_of(src):
     flags = ['-O3', '-std=c++17', '--offload-arch=gfx950', '--cuda-device-only', '-S', '-o', '-']
-    if os.path.basename(src) in ('nms.hip', 'quant.hip', 'loss.hip', 'calib.hip', 'qat.hip', 'tpsq.hip', 'resize.hip', 'tta.hip', 'evalmatch.hip', 'cocoeval.hip', 'ema.hip'):
+    if os.path.basename(src) in ('nms.hip', 'quant.hip', 'loss.hip', 'calib.hip', 'qat.hip', 'tpsq.hip', 'resize.hip', 'tta.hip', 'evalmatch.hip', 'cocoeval.hip', 'ema.hip', 'kd.hip'):
         flags.insert(0, '-ffp-contract=off')
     asm = subprocess.run([HIPCC] + flags + [src], check=True, capture_output=True, text=True, cwd=CSRC).stdout
     meta = asm[asm.index('amdhsa.kernels:'):] if 'amdhsa.kernels:' in asm else ''

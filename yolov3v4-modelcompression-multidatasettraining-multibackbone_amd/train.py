@@ -33,7 +33,7 @@ from models import Darknet, attempt_download, load_darknet_weights
 from utils import torch_utils
 from utils.datasets import LoadImagesAndLabels
 from utils.parse_config import parse_data_cfg
-from utils.utils import (compute_loss, compute_lost_KD, fitness, init_seeds, labels_to_class_weights, labels_to_image_weights,
+from utils.utils import (compute_loss, compute_lost_KD, compute_lost_KD2, compute_lost_KD3, compute_lost_KD4,fitness, init_seeds, labels_to_class_weights, labels_to_image_weights,
                          plot_images, plot_results, strip_optimizer)
 
 try:
@@ -65,6 +65,41 @@ def load_teacher(t_cfg, t_weights, device):
     else:
         raise Exception('pls provide proper teacher weights for knowledge distillation')
     return t_model.eval()
+
+
+KD5_REASON = ('knowledge-distillation strategy 5 (fine-grained feature imitation) is not carried over: the reference\'s mask builder '
+              '(utils/utils.py fine_grained_imitation_feature_mask) calls .cuda() unconditionally, so it cannot be run and recorded '
+              'without an NVIDIA device and there is nothing to pin a port to')
+
+
+def configure_distillation(model, t_model, strategy, device):
+    """Checks of ``--KDstr`` before the first step.  The teacher must be a float graph: its heads and features are the targets.
+    Strategy 4 on a GPU: both models hand out the channel-summed attention maps of ``feature_out`` instead of ~70 NCHW fp32 copies
+    per step (``hip_return_features = 'attention'``, engine/kd.py); on the CPU the eager feature lists are used as they are."""
+    if t_model is None:
+        return
+    if strategy == 5:
+        raise NotImplementedError(KD5_REASON)
+    if strategy not in (1, 2, 3, 4):
+        raise NotImplementedError('knowledge-distillation strategy %s does not exist (1 - 4 are carried over)' % strategy)
+    if getattr(t_model, 'quantized', -1) != -1:
+        raise ValueError('the distillation teacher must be a float graph (quantized == -1), got quantized = %s' % t_model.quantized)
+    if strategy == 4 and torch.device(device).type != 'cpu':
+        model.hip_return_features = t_model.hip_return_features = 'attention'
+
+
+def distillation_loss(strategy, model, targets, pred, output_t, feature_s, feature_t, nc, batch):
+    """The distillation term of reference train.py:395-413 for ``--KDstr`` 1 - 4 (KD2 also returns reg_ratio, which the reference
+    only prints)."""
+    if strategy == 1:
+        return compute_lost_KD(pred, output_t, nc, batch)
+    if strategy == 2:
+        return compute_lost_KD2(model, targets, pred, output_t)[0]
+    if strategy == 3:
+        return compute_lost_KD3(model, targets, pred, output_t)
+    if strategy == 4:
+        return compute_lost_KD4(model, targets, pred, output_t, feature_s, feature_t, batch)
+    raise NotImplementedError(KD5_REASON if strategy == 5 else 'knowledge-distillation strategy %s does not exist' % strategy)
 
 
 def build_optimizer(model, opt, hyp, device):
@@ -155,6 +190,7 @@ def train(opt, hyp):
     model = Darknet(cfg, quantized=opt.quantized, a_bit=opt.a_bit, w_bit=opt.w_bit, steps=steps, is_gray_scale=opt.gray_scale,
                     maxabsscaler=opt.maxabsscaler, shortcut_way=opt.shortcut_way).to(device)
     t_model = load_teacher(opt.t_cfg, opt.t_weights, device) if opt.t_cfg else None
+    configure_distillation(model, t_model, opt.KDstr, device)
 
     optimizer = build_optimizer(model, opt, hyp, device)
 
@@ -319,10 +355,9 @@ def train(opt, hyp):
                 return results
             if t_model is not None:
                 with torch.no_grad():
-                    _, output_t, _ = t_model(imgs)
-                if opt.KDstr != 1:
-                    raise NotImplementedError('only knowledge-distillation strategy 1 (soft targets) is carried over')
-                loss = loss + compute_lost_KD(pred, output_t, nc, imgs.size(0))
+                    _, output_t, feature_t = t_model(imgs)
+                loss = loss + distillation_loss(opt.KDstr, model, targets, [p.float() for p in pred], output_t, feature_s, feature_t,
+                                                nc, imgs.size(0))
 
             loss = loss * (batch_size * (world if distributed else 1) / 64)
             scaler.scale(loss).backward()
@@ -451,6 +486,8 @@ def parse_args(argv=None):
     """``make_parser().parse_args(argv)`` plus the combinations the parser refuses."""
     parser = make_parser()
     opt = parser.parse_args(argv)
+    if opt.KDstr in (2, 3, 4) and not opt.t_cfg:
+        parser.error('--KDstr %d distils from a teacher: give --t_cfg and --t_weights' % opt.KDstr)
     if opt.device_cache:
         for flag, on in (('--cache-images', opt.cache_images), ('--host-augment', opt.host_augment), ('--rect', opt.rect),
                          ('--image-arith cv2', opt.image_arith == 'cv2')):

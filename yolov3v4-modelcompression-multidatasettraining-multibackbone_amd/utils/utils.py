@@ -287,6 +287,90 @@ def compute_lost_KD(output_s, output_t, num_classes, batch_size):
     return kl * (T * T) / batch_size * weight
 
 
+def _kd_head_terms(model, targets, output_s, output_t, margin=None):
+    """The head terms KD2 - KD4 share (reference utils.py:446-552), operation for operation: per yolo layer the squared distance
+    between the student's and the teacher's decoded boxes at the label cells (``margin`` None), or - KD2 - the student's distance
+    to the label wherever it exceeds the teacher's by more than ``margin`` (Chen et al.'s teacher-bounded regression); plus the
+    soft-target KL over the objectness + class logits of every cell.  Returns (lcls, lbox, reg_num, reg_nb)."""
+    T = 3.0
+    criterion_st = nn.KLDivLoss(reduction='sum')
+    dev = output_s[0].device
+    lcls, lbox = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
+    tcls, tbox, indices, anchor_vec = build_targets(output_s, targets, model)
+    reg_num, reg_nb = 0, 0
+    for i, (ps, pt) in enumerate(zip(output_s, output_t)):
+        b, a, gj, gi = indices[i]
+        nb = len(b)
+        if nb:
+            pss = ps[b, a, gj, gi]
+            pts = pt[b, a, gj, gi]
+            psxy = torch.sigmoid(pss[:, 0:2])
+            psbox = torch.cat((psxy, torch.exp(pss[:, 2:4]) * anchor_vec[i]), 1).view(-1, 4)
+            ptxy = torch.sigmoid(pts[:, 0:2])
+            ptbox = torch.cat((ptxy, torch.exp(pts[:, 2:4]) * anchor_vec[i]), 1).view(-1, 4)
+            if margin is None:
+                l2_dis = (psbox - ptbox).pow(2).sum(1)
+                lbox += l2_dis.sum()
+            else:
+                l2_dis_s = (psbox - tbox[i]).pow(2).sum(1)
+                l2_dis_s_m = l2_dis_s + margin
+                l2_dis_t = (ptbox - tbox[i]).pow(2).sum(1)
+                l2_num = l2_dis_s_m > l2_dis_t
+                lbox += l2_dis_s[l2_num].sum()
+                reg_num += l2_num.sum().item()
+                reg_nb += nb
+        output_s_i = ps[..., 4:].reshape(-1, model.nc + 1)
+        output_t_i = pt[..., 4:].reshape(-1, model.nc + 1)
+        lcls += criterion_st(F.log_softmax(output_s_i / T, dim=1), F.softmax(output_t_i / T, dim=1)) * (T * T) / ps.size(0)
+    return lcls, lbox, reg_num, reg_nb
+
+
+def compute_lost_KD2(model, targets, output_s, output_t):
+    """Strategy 2 (reference utils.py:446-487): soft targets per head + teacher-bounded box regression.  Returns
+    ``(loss, reg_ratio)``, reg_ratio the share of label cells where the student is further from the label than the teacher."""
+    Lambda_cls, Lambda_box = 0.0001, 0.001
+    lcls, lbox, reg_num, reg_nb = _kd_head_terms(model, targets, output_s, output_t, margin=0.0)
+    reg_ratio = reg_num / reg_nb if reg_nb else 0
+    return lcls * Lambda_cls + lbox * Lambda_box, reg_ratio
+
+
+def compute_lost_KD3(model, targets, output_s, output_t):
+    """Strategy 3 (reference utils.py:490-521): soft targets per head + the distance between student and teacher boxes."""
+    Lambda_cls, Lambda_box = 0.0001, 0.001
+    lcls, lbox, _, _ = _kd_head_terms(model, targets, output_s, output_t)
+    return lcls * Lambda_cls + lbox * Lambda_box
+
+
+def compute_lost_KD4(model, targets, output_s, output_t, feature_s, feature_t, batch_size):
+    """Strategy 4 (reference utils.py:524-564): the head terms of strategy 3 with Lambda_cls = 0.001, plus attention transfer over
+    ``feature_out``: per feature KLDivLoss(sum) between the softmax over pixels of the student's and the teacher's channel-summed
+    maps ``abs().sum(1)``, at temperature 3, times T * T / batch_size.  Channel counts may differ (a pruned student); counts and
+    spatial sizes may not (``ValueError``, where the reference prints "feature mismatch!" and exits).
+
+    An element of ``feature_s`` / ``feature_t`` is the reference's 4-D feature or an already channel-summed (N, H, W) map.  When
+    both arguments are ``engine.kd.AttentionMaps`` of one layout on one GPU - what ``hip_return_features = 'attention'`` returns -
+    the term is one ``yh_kd_attention_kl`` call (engine/kd.py; ``YOLO_HIP_KD=0`` keeps the statement below on the maps)."""
+    T = 3.0
+    Lambda_cls, Lambda_box, Lambda_feature = 0.001, 0.001, 0.001
+    lcls, lbox, _, _ = _kd_head_terms(model, targets, output_s, output_t)
+    if len(feature_t) != len(feature_s):
+        raise ValueError('feature mismatch: %d student features, %d teacher features' % (len(feature_s), len(feature_t)))
+    for fs, ft in zip(feature_s, feature_t):
+        if fs.shape[0] != ft.shape[0] or tuple(fs.shape[-2:]) != tuple(ft.shape[-2:]):
+            raise ValueError('feature mismatch: student %s, teacher %s' % (tuple(fs.shape), tuple(ft.shape)))
+    from engine import kd
+    if kd.fusable(feature_s, feature_t):
+        lfeature = kd.attention_kl(feature_s, feature_t, batch_size, T)
+    else:
+        criterion_stf = nn.KLDivLoss(reduction='sum')
+        lfeature = torch.zeros(1, device=output_s[0].device)
+        for fs, ft in zip(feature_s, feature_t):
+            ft = (ft if ft.dim() == 3 else ft.abs().sum(1)).reshape(ft.size(0), -1)
+            fs = (fs if fs.dim() == 3 else fs.abs().sum(1)).reshape(fs.size(0), -1)
+            lfeature += criterion_stf(F.log_softmax(fs / T, dim=1), F.softmax(ft / T, dim=1)) * (T * T) / batch_size
+    return lcls * Lambda_cls + lbox * Lambda_box + lfeature * Lambda_feature
+
+
 # -------------------------------------------------------------------------------------------------- NMS
 def nms_greedy(boxes, scores, iou_thres):
     """Host restatement of torchvision.ops.boxes.nms (see module docstring). Returns LongTensor."""

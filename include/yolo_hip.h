@@ -486,6 +486,29 @@ int yh_yolo_loss_bwd(const yh_loss_desc* d, void* stream);
  * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
 int yh_yolo_loss_focal_fwd(const yh_loss_desc* d, float gamma, float alpha, void* stream);
 int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float alpha, void* stream);
+/* The same loss with another box measure in place of GIoU (darknet's iou_loss=diou / ciou, the YOLOv4 cfgs): the measure of
+ * utils.bbox_iou(x1y1x2y2=False, DIoU=True / CIoU=True), in its operation order, serves lbox = sum (1 - measure) AND the objectness
+ * target tobj = (1 - gr) + gr * max(measure, 0).  With the predicted box a = (ax1, ay1, ax2, ay2), the label b, their widths and
+ * heights w1, h1 / w2, h2, iou as for GIoU and cw, ch the sides of the smallest enclosing box:
+ *   c2   = cw^2 + ch^2 + 1e-16
+ *   rho2 = ((bx1 + bx2) - (ax1 + ax2))^2 / 4 + ((by1 + by2) - (ay1 + ay2))^2 / 4
+ *   DIoU = iou - rho2 / c2
+ *   v    = (4 / pi^2) * (atan(w2 / h2) - atan(w1 / h1))^2,   alpha_c = v / (1 - iou + v)
+ *   CIoU = iou - (rho2 / c2 + v * alpha_c)
+ * alpha_c is a constant for the derivative (the statement's torch.no_grad()): d CIoU = d iou - d(rho2 / c2) - alpha_c * dv,
+ * dv = (8 / pi^2) (atan(w2 / h2) - atan(w1 / h1)) * (-d atan(w1 / h1)), d atan(u) = du / (1 + u^2); clamp(max=1e3) cuts the width
+ * and height gradients as for GIoU.  Where 1 - iou + v <= 0 - the prediction equals its label exactly, iou == 1 and v == 0 in fp32 -
+ * alpha_c is 0, the limit of v * alpha_c, and value and gradient stay finite.  That is a deliberate difference from the torch
+ * statement, which computes 0 / 0 there and returns NaN for both.  Everywhere else the entries follow the statement; a NaN logit
+ * propagates.
+ * box is one of YH_BOX_*; YH_BOX_GIOU computes what yh_yolo_loss_fwd / _bwd (gamma == 0) and yh_yolo_loss_focal_fwd / _bwd (gamma > 0)
+ * compute.  gamma == 0: plain BCE, alpha (FocalLoss's) is ignored; gamma > 0: the focal element above, under its rules for gamma and
+ * alpha.  box outside 0..2, a negative or non-finite gamma and everything yh_yolo_loss_fwd / _bwd refuse: YH_EINVAL before any launch.
+ * Label smoothing needs no entry: cp = 1 - eps / 2 and cn = eps / 2 in the descriptor, every entry takes soft class targets.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+enum { YH_BOX_GIOU = 0, YH_BOX_DIOU = 1, YH_BOX_CIOU = 2 };
+int yh_yolo_loss_box_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream);
+int yh_yolo_loss_box_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream);
 
 /* Backward of the depthwise block and of squeeze-excite (training of the Mobilenet / Ghost backbones).
  *  yh_dw_wgrad   dw[c][r][s] += sum_pixels dz[p][c] * x[p shifted by (r, s)][c]   (fp32 [c][k][k], caller zeroes)

@@ -71,8 +71,25 @@ __device__ __forceinline__ float loss_elem_grad(float x, float t, float pw, floa
     return a * (bce_grad(x, t, pw) * M + (bce(x, t, pw) / q) * M * gamma * u * s * (1.f - s));
 }
 
-// GIoU of the predicted box (from 4 raw logits, xywh) against the target (xywh), bbox_iou(x1y1x2y2=False, GIoU=True)
-__device__ __forceinline__ Dual4 giou_of(const float* ps4, const float* an, const float* tb) {
+// d atan(u) = du / (1 + u^2)
+__device__ __forceinline__ Dual4 datan(const Dual4& a) {
+    Dual4 r;
+    const float inv = 1.f / (1.f + a.v * a.v);
+    r.v = atanf(a.v);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.d[i] = a.d[i] * inv;
+    return r;
+}
+
+// The box measure of the predicted box (from 4 raw logits, xywh) against the target (xywh): bbox_iou(x1y1x2y2=False, ...) with
+// GIoU=True (BOX == YH_BOX_GIOU, the default loss), DIoU=True or CIoU=True, in the statement's operation order:
+//   c2 = cw^2 + ch^2 + 1e-16,  rho2 = ((bx1 + bx2) - (ax1 + ax2))^2 / 4 + (the same in y),  DIoU = iou - rho2 / c2
+//   v = (4 / pi^2) (atan(w2 / h2) - atan(w1 / h1))^2,  alpha = v / (1 - iou + v),  CIoU = iou - (rho2 / c2 + v * alpha)
+// alpha is a constant for the derivative (the statement's torch.no_grad()).  Where 1 - iou + v <= 0 - the prediction equals its label
+// exactly: iou == 1 and v == 0 in fp32 - alpha is 0, the limit of v * alpha; the statement divides 0 by 0 there and returns NaN for
+// value and gradient.  A NaN logit fails `<= 0` and propagates.
+template <int BOX>
+__device__ __forceinline__ Dual4 box_measure_of(const float* ps4, const float* an, const float* tb) {
     Dual4 px = mk(sigmoidf(ps4[0])), py = mk(sigmoidf(ps4[1]));
     px.d[0] = px.v * (1.f - px.v);
     py.d[1] = py.v * (1.f - py.v);
@@ -88,8 +105,23 @@ __device__ __forceinline__ Dual4 giou_of(const float* ps4, const float* an, cons
     const Dual4 uni = (w1 * h1 + mk(1e-16f)) + w2 * h2 - inter;
     const Dual4 iou = inter / uni;
     const Dual4 cw = dmax(ax2, bx2) - dmin(ax1, bx1), ch = dmax(ay2, by2) - dmin(ay1, by1);
-    const Dual4 hull = cw * ch + mk(1e-16f);
-    return iou - (hull - uni) / hull;
+    if constexpr (BOX == YH_BOX_GIOU) {
+        const Dual4 hull = cw * ch + mk(1e-16f);
+        return iou - (hull - uni) / hull;
+    } else {
+        const Dual4 c2 = (cw * cw + ch * ch) + mk(1e-16f);
+        const Dual4 dx = (bx1 + bx2) - (ax1 + ax2), dy = (by1 + by2) - (ay1 + ay2);
+        const Dual4 rho2 = (dx * dx) * mk(0.25f) + (dy * dy) * mk(0.25f);
+        if constexpr (BOX == YH_BOX_DIOU) {
+            return iou - rho2 / c2;
+        } else {
+            const Dual4 da = mk(atanf(w2.v / h2.v)) - datan(w1 / h1);
+            const Dual4 v = mk(0.40528473456935116f) * (da * da);                   // 4 / pi^2
+            const float den = (1.f - iou.v) + v.v;
+            const Dual4 alpha = mk(den <= 0.f ? 0.f : v.v / den);
+            return iou - (rho2 / c2 + v * alpha);
+        }
+    }
 }
 
 __device__ __forceinline__ void block_sum_atomic(float v, float* dst) {
@@ -146,7 +178,8 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const yh_loss_desc d) 
 // matched candidates, forward: box and class sums, objectness targets.  One thread per (candidate, class) - the class loop of a
 // candidate used to run inside one thread (80 dependent global loads + BCEs: 33 - 83 us for 1536 threads, latency bound); the thread
 // of class 0 also takes the box term.  nc == 1: one thread per candidate, no class term (as the reference, utils.py:412).
-template <bool FOCAL>
+// BOX selects the box measure (box_measure_of); it is the statement's one variable, so the objectness target takes it too.
+template <bool FOCAL, int BOX>
 __global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -157,7 +190,7 @@ __global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_des
         const float* ps = d.p + m.b * d.sb + m.a * d.sa + m.gy * d.sy + m.gx * d.sx;
         if (c == 0) {
             const float box[4] = {ps[0], ps[1], ps[2], ps[3]};
-            const Dual4 g = giou_of(box, m.an, m.tb);
+            const Dual4 g = box_measure_of<BOX>(box, m.an, m.tb);
             lbox = 1.f - g.v;
             if (d.winner[m.cell] == k) d.tobj[m.cell] = (1.f - d.gr) + d.gr * fmaxf(g.v, 0.f);
         }
@@ -244,7 +277,7 @@ __global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc 
 
 // matched candidates, backward: box and class terms added on top of the dense pass (duplicates of a cell accumulate); one thread per
 // (candidate, class) as in the forward
-template <bool FOCAL>
+template <bool FOCAL, int BOX>
 __global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -257,7 +290,7 @@ __global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_des
     if (c == 0) {
         const float w_box = *d.scale * d.g_box / (float)nb;
         const float box[4] = {ps[0], ps[1], ps[2], ps[3]};
-        const Dual4 g = giou_of(box, m.an, m.tb);
+        const Dual4 g = box_measure_of<BOX>(box, m.an, m.tb);
 #pragma unroll
         for (int i = 0; i < 4; ++i) atomicAdd(gp + i, -w_box * g.d[i]);
     }
@@ -285,28 +318,50 @@ static int check_focal(float gamma, float alpha) {
     return YH_OK;
 }
 
-template <bool FOCAL>
+template <bool FOCAL, int BOX>
 static int loss_fwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
     if (d->nt > 0) {
         const unsigned blocks = (unsigned)(((long)d->na * d->nt + 255) / 256);
         const unsigned cblocks = (unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256);
         hipLaunchKernelGGL(loss_assign_kernel, dim3(blocks), dim3(256), 0, s, *d);
-        hipLaunchKernelGGL((loss_matched_fwd_kernel<FOCAL>), dim3(cblocks), dim3(256), 0, s, *d, gamma, alpha);
+        hipLaunchKernelGGL((loss_matched_fwd_kernel<FOCAL, BOX>), dim3(cblocks), dim3(256), 0, s, *d, gamma, alpha);
     }
     if ((long)d->bs * d->na * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
     hipLaunchKernelGGL((loss_obj_fwd_kernel<FOCAL>), dim3(grid_n((long)d->bs * d->na * d->ny * d->nx)), dim3(256), 0, s, *d, gamma, alpha);
     return check_launch();
 }
 
-template <bool FOCAL>
+template <bool FOCAL, int BOX>
 static int loss_bwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
     if ((long)d->bs * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
     const long pixels = (long)d->bs * d->ny * d->nx;
     hipLaunchKernelGGL((loss_dense_bwd_kernel<FOCAL>), dim3((unsigned)(pixels < 16384 ? pixels : 16384)), dim3(256), 0, s, *d, gamma, alpha);
     if (d->nt > 0)
-        hipLaunchKernelGGL((loss_matched_bwd_kernel<FOCAL>), dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)),
+        hipLaunchKernelGGL((loss_matched_bwd_kernel<FOCAL, BOX>), dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)),
                            dim3(256), 0, s, *d, gamma, alpha);
     return check_launch();
+}
+
+// the yh_yolo_loss_box_* entries: box kind 0..2; gamma finite and >= 0 (0: plain BCE, alpha ignored), gamma > 0 under check_focal
+static int check_box(int box, float gamma, float alpha) {
+    if (box < YH_BOX_GIOU || box > YH_BOX_CIOU || !std::isfinite(gamma) || gamma < 0.f) return YH_EINVAL;
+    return gamma > 0.f ? check_focal(gamma, alpha) : YH_OK;
+}
+
+template <int BOX>
+static int loss_box(const yh_loss_desc* d, bool bwd, float gamma, float alpha, hipStream_t s) {
+    if (gamma > 0.f) return bwd ? loss_bwd<true, BOX>(d, gamma, alpha, s) : loss_fwd<true, BOX>(d, gamma, alpha, s);
+    return bwd ? loss_bwd<false, BOX>(d, 0.f, 0.f, s) : loss_fwd<false, BOX>(d, 0.f, 0.f, s);
+}
+
+static int loss_box_entry(const yh_loss_desc* d, bool bwd, int box, float gamma, float alpha, void* stream) {
+    int rc = check_loss(d, bwd);
+    if (!rc) rc = check_box(box, gamma, alpha);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (box == YH_BOX_DIOU) return loss_box<YH_BOX_DIOU>(d, bwd, gamma, alpha, s);
+    if (box == YH_BOX_CIOU) return loss_box<YH_BOX_CIOU>(d, bwd, gamma, alpha, s);
+    return loss_box<YH_BOX_GIOU>(d, bwd, gamma, alpha, s);
 }
 
 }  // namespace yh
@@ -316,25 +371,33 @@ using namespace yh;
 extern "C" int yh_yolo_loss_fwd(const yh_loss_desc* d, void* stream) {
     int rc = check_loss(d, false);
     if (rc) return rc;
-    return loss_fwd<false>(d, 0.f, 0.f, (hipStream_t)stream);
+    return loss_fwd<false, YH_BOX_GIOU>(d, 0.f, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int yh_yolo_loss_bwd(const yh_loss_desc* d, void* stream) {
     int rc = check_loss(d, true);
     if (rc) return rc;
-    return loss_bwd<false>(d, 0.f, 0.f, (hipStream_t)stream);
+    return loss_bwd<false, YH_BOX_GIOU>(d, 0.f, 0.f, (hipStream_t)stream);
 }
 
 extern "C" int yh_yolo_loss_focal_fwd(const yh_loss_desc* d, float gamma, float alpha, void* stream) {
     int rc = check_loss(d, false);
     if (!rc) rc = check_focal(gamma, alpha);
     if (rc) return rc;
-    return loss_fwd<true>(d, gamma, alpha, (hipStream_t)stream);
+    return loss_fwd<true, YH_BOX_GIOU>(d, gamma, alpha, (hipStream_t)stream);
 }
 
 extern "C" int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float alpha, void* stream) {
     int rc = check_loss(d, true);
     if (!rc) rc = check_focal(gamma, alpha);
     if (rc) return rc;
-    return loss_bwd<true>(d, gamma, alpha, (hipStream_t)stream);
+    return loss_bwd<true, YH_BOX_GIOU>(d, gamma, alpha, (hipStream_t)stream);
+}
+
+extern "C" int yh_yolo_loss_box_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream) {
+    return loss_box_entry(d, false, box, gamma, alpha, stream);
+}
+
+extern "C" int yh_yolo_loss_box_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream) {
+    return loss_box_entry(d, true, box, gamma, alpha, stream);
 }

@@ -374,6 +374,8 @@ _SIGNATURES = {
     'yh_yolo_loss_bwd': (C.c_int, [C.POINTER(LossDesc), _vp]),
     'yh_yolo_loss_focal_fwd': (C.c_int, [C.POINTER(LossDesc), _f32, _f32, _vp]),
     'yh_yolo_loss_focal_bwd': (C.c_int, [C.POINTER(LossDesc), _f32, _f32, _vp]),
+    'yh_yolo_loss_box_fwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _vp]),
+    'yh_yolo_loss_box_bwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _vp]),
     'yh_nchw_to_nhwc': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'yh_letterbox_fwd': (C.c_int, [C.POINTER(LetterboxDesc), _vp]),
     'yh_resize_bilinear': (C.c_int, [C.POINTER(ResizeDesc), _vp]),

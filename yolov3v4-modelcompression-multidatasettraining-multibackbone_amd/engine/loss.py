@@ -16,6 +16,13 @@ entries ``yh_yolo_loss_focal_fwd`` / ``_bwd``: the same launches with the focal 
 sums, counts, normalisation and label check.  ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for focal loss (A/B runs);
 ``stats()`` counts the focal calls.  Where a logit is saturated on the side of its 0 / 1 target the kernels return the limit 0 and
 stay finite; fp32 torch returns inf / nan there for gamma < 1 (include/yolo_hip.h).
+
+``model.box_loss`` in ``('diou', 'ciou')`` (darknet's ``iou_loss``, ``train.py --box-loss``) takes the node through
+``yh_yolo_loss_box_fwd`` / ``_bwd``: the matched kernels with that box measure in ``lbox`` and in the objectness target, with or
+without the focal element.  GIoU keeps the entries above.  ``YOLO_HIP_BOX_LOSS=0`` keeps the torch statement for DIoU / CIoU (A/B
+runs); ``box_stats()`` counts the calls.  Where a prediction equals its label exactly the CIoU kernels take ``alpha = 0`` and stay
+finite; the torch statement returns nan there (include/yolo_hip.h).  ``hyp['label_smoothing']`` only changes the two
+class targets ``cp`` / ``cn`` of the descriptor, so it never leaves the fused path.
 """
 import ctypes as C
 import os
@@ -28,6 +35,8 @@ from .hiplib import LossDesc
 _LIB_OVERRIDE = None   # tests inject the host emulation here
 FOCAL_ALPHA = 0.25     # utils.utils.compute_loss builds FocalLoss(bce, fl_gamma) with the class's default alpha
 _STATS = dict(focal_fwd=0, focal_bwd=0)
+BOX_KINDS = {'giou': 0, 'diou': 1, 'ciou': 2}      # YH_BOX_* of include/yolo_hip.h
+_BOX_STATS = dict(box_fwd=0, box_bwd=0)
 
 
 def _lib():
@@ -44,12 +53,32 @@ def reset_stats():
         _STATS[k] = 0
 
 
+def box_stats():
+    """Counters since ``reset_box_stats``: calls of ``yh_yolo_loss_box_fwd`` / ``_bwd`` (one per head and pass, DIoU / CIoU only)."""
+    return dict(_BOX_STATS)
+
+
+def reset_box_stats():
+    for k in _BOX_STATS:
+        _BOX_STATS[k] = 0
+
+
+def box_kind(model):
+    """``model.box_loss`` ('giou' when the model has none) as YH_BOX_*; an unknown kind raises ValueError naming it."""
+    kind = getattr(model, 'box_loss', 'giou')
+    if kind not in BOX_KINDS:
+        raise ValueError('unknown box loss %r: expected one of %s' % (kind, ', '.join(BOX_KINDS)))
+    return BOX_KINDS[kind]
+
+
 def usable(p, model):
     """Fused path: CUDA (or an injected emulator), fp32 raw heads with unit stride on the last axis; focal loss too unless
-    ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for it."""
+    ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for it, DIoU / CIoU too unless ``YOLO_HIP_BOX_LOSS=0`` does."""
     if _LIB_OVERRIDE is None and not p[0].is_cuda:
         return False
     if model.hyp.get('fl_gamma', 0.0) > 0 and os.environ.get('YOLO_HIP_FOCAL_LOSS', '1') == '0':
+        return False
+    if box_kind(model) != BOX_KINDS['giou'] and os.environ.get('YOLO_HIP_BOX_LOSS', '1') == '0':
         return False
     return all(t.dtype == torch.float32 and t.dim() == 5 and t.stride(4) == 1 for t in p)
 
@@ -119,7 +148,11 @@ class _YoloLoss(torch.autograd.Function):
                          bs=bs, na=na, ny=ny, nx=nx, no=no, nc=no - 5, nt=nt, iou_t=meta['iou_t'], gr=meta['gr'],
                          cp=meta['cp'], cn=meta['cn'], cls_pw=meta['cls_pw'], obj_pw=meta['obj_pw'],
                          g_box=meta['giou'], g_obj=meta['obj'], g_cls=meta['cls'])
-            if meta['gamma'] > 0:
+            if meta['box']:
+                hiplib.check(lib.yh_yolo_loss_box_fwd(C.byref(d), meta['box'], meta['gamma'], meta['alpha'], hiplib.stream_ptr()), 'yh_yolo_loss_box_fwd')
+                _BOX_STATS['box_fwd'] += 1
+                _STATS['focal_fwd'] += meta['gamma'] > 0
+            elif meta['gamma'] > 0:
                 hiplib.check(lib.yh_yolo_loss_focal_fwd(C.byref(d), meta['gamma'], meta['alpha'], hiplib.stream_ptr()), 'yh_yolo_loss_focal_fwd')
                 _STATS['focal_fwd'] += 1
             else:
@@ -143,6 +176,7 @@ class _YoloLoss(torch.autograd.Function):
             flush_label_check()
         ctx.heads, ctx.keep_fwd = heads, (targets, counts, meta['anchors'])
         ctx.focal = (meta['gamma'], meta['alpha'])
+        ctx.box = meta['box']
         loss = lbox + lobj + lcls
         ctx.mark_non_differentiable(lbox, lobj, lcls)
         return loss, lbox, lobj, lcls
@@ -167,7 +201,11 @@ class _YoloLoss(torch.autograd.Function):
             d.grad, d.scale = hiplib.ptr(g), hiplib.ptr(scale)
             d.gb, d.ga, d.gy, d.gx = g.stride(0), g.stride(1), g.stride(2), g.stride(3)
             with hiplib.on_device(p):
-                if gamma > 0:
+                if ctx.box:
+                    hiplib.check(lib.yh_yolo_loss_box_bwd(C.byref(d), ctx.box, gamma, alpha, hiplib.stream_ptr()), 'yh_yolo_loss_box_bwd')
+                    _BOX_STATS['box_bwd'] += 1
+                    _STATS['focal_bwd'] += gamma > 0
+                elif gamma > 0:
                     hiplib.check(lib.yh_yolo_loss_focal_bwd(C.byref(d), gamma, alpha, hiplib.stream_ptr()), 'yh_yolo_loss_focal_bwd')
                     _STATS['focal_bwd'] += 1
                 else:
@@ -181,13 +219,13 @@ def compute_loss(p, targets, model, yolo_modules, smooth_bce):
     """Same contract as utils.utils.compute_loss: ``(loss[1], detached [lbox, lobj, lcls, loss])``."""
     flush_label_check()
     h = model.hyp
-    cp, cn = smooth_bce(eps=0.0)
+    cp, cn = smooth_bce(eps=float(h.get('label_smoothing', 0.0)))
     dev = p[0].device
     anchors = [layer.anchor_vec.to(device=dev, dtype=torch.float32).contiguous() for layer in yolo_modules(model)]
     meta = dict(targets=targets.to(device=dev, dtype=torch.float32).contiguous(), anchors=anchors, iou_t=float(h['iou_t']),
                 gr=float(model.gr), cp=float(cp), cn=float(cn), cls_pw=float(h['cls_pw']),
                 obj_pw=float(h['obj_pw']), giou=float(h['giou']), obj=float(h['obj']), cls=float(h['cls']),
-                gamma=float(h.get('fl_gamma', 0.0)), alpha=FOCAL_ALPHA)
+                gamma=float(h.get('fl_gamma', 0.0)), alpha=FOCAL_ALPHA, box=box_kind(model))
     bases = _head_bases(p)
     with hiplib.on_device(p[0]):
         if bases is not None:

@@ -163,6 +163,8 @@ def train(opt, hyp):
         hyp['fl_gamma'] = opt.fl_gamma
     if hyp['fl_gamma'] and _is_main(opt.local_rank):
         print('Using FocalLoss(gamma=%g)' % hyp['fl_gamma'])      # reference train.py:52-53
+    if getattr(opt, 'label_smoothing', None) is not None:
+        hyp['label_smoothing'] = opt.label_smoothing
 
     # one process per GPU; the launcher provides the rendezvous (train.py:96-110 hard-codes nccl + tcp://127.0.0.1:9999)
     rank, world = opt.local_rank, int(os.environ.get('WORLD_SIZE', '1'))
@@ -263,8 +265,14 @@ def train(opt, hyp):
         testloader = DataLoader(testset, batch_size=max(batch_size // 4, 1), num_workers=nw, pin_memory=device.type != 'cpu',
                                 collate_fn=testset.collate_fn)
 
+    box_loss = getattr(opt, 'box_loss', 'giou')
+    if box_loss == 'cfg':
+        box_loss = box_loss_of_cfg(core.module_defs)
+    if (box_loss != 'giou' or hyp.get('label_smoothing', 0.0)) and _is_main(rank):
+        print('Using box loss %s, label smoothing %g' % (box_loss, hyp.get('label_smoothing', 0.0)))
     for m in {model, core}:
         m.nc, m.hyp, m.gr = nc, hyp, 1.0
+        m.box_loss = box_loss      # an attribute like gr, not a hyp entry: print_mutation formats every hyp value with %g
         m.class_weights = labels_to_class_weights(dataset.labels, nc).to(device)
     ema = torch_utils.ModelEMA(core) if opt.ema else None
 
@@ -432,6 +440,27 @@ def _focal_gamma(text):
     return v
 
 
+def _label_smoothing(text):
+    """--label-smoothing: a finite float in [0, 1)."""
+    v = float(text)
+    if not math.isfinite(v) or v < 0 or v >= 1:
+        raise argparse.ArgumentTypeError('must be a finite number in [0, 1), got %r' % text)
+    return v
+
+
+def box_loss_of_cfg(module_defs):
+    """--box-loss cfg: the ``iou_loss`` key of the cfg's ``[yolo]`` sections; 'giou' when none carries it.  Sections that disagree, or
+    a value other than giou / diou / ciou (darknet also knows mse and iou: refused, not approximated), raise ValueError naming it."""
+    seen = sorted({str(d['iou_loss']).strip().lower() for d in module_defs if d['type'] == 'yolo' and 'iou_loss' in d})
+    if not seen:
+        return 'giou'
+    if len(seen) > 1:
+        raise ValueError('the [yolo] sections of the cfg disagree on iou_loss: %s' % ', '.join(seen))
+    if seen[0] not in ('giou', 'diou', 'ciou'):
+        raise ValueError('iou_loss=%s of the cfg is not supported: expected giou, diou or ciou' % seen[0])
+    return seen[0]
+
+
 def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--epochs', type=int, default=300)
@@ -466,6 +495,13 @@ def make_parser():
     parser.add_argument('--fl-gamma', type=_focal_gamma, default=None,
                         help="focal loss gamma (0: plain BCE); default: the hyp dict's fl_gamma.  On a GPU the fused loss kernels "
                              'carry it (YOLO_HIP_FOCAL_LOSS=0 keeps the torch statement)')
+    parser.add_argument('--box-loss', choices=['giou', 'diou', 'ciou', 'cfg'], default='giou',
+                        help="box regression measure of compute_loss (and of its objectness target); 'cfg' takes the iou_loss key of "
+                             "the cfg's [yolo] sections (the YOLOv4 cfgs say ciou; none: giou).  On a GPU the fused loss kernels carry "
+                             'all three (YOLO_HIP_BOX_LOSS=0 keeps the torch statement for diou / ciou)')
+    parser.add_argument('--label-smoothing', type=_label_smoothing, default=None,
+                        help="label smoothing eps of the class targets (1 - eps / 2, eps / 2), 0 <= eps < 1; default: the hyp dict's "
+                             'label_smoothing or 0')
     parser.add_argument('--pretrain', '-pt', dest='pt', action='store_true', help='load the whole darknet weights file')
     parser.add_argument('--mixedprecision', '-mpt', dest='mpt', action='store_true', help='mixed precision training')
     parser.add_argument('--s', type=float, default=0.001, help='scale sparse rate')

@@ -234,13 +234,24 @@ def _fused_loss_override():
     return hip_loss._LIB_OVERRIDE is not None
 
 
+BOX_LOSSES = {'giou': 'GIoU', 'diou': 'DIoU', 'ciou': 'CIoU'}      # model.box_loss -> the bbox_iou flag
+
+
 def compute_loss(p, targets, model, fused=None):
     """GIoU box loss + objectness BCE + class BCE over the raw head tensors (reference utils.py:368-432).
 
     Returns ``(loss, detached [lbox, lobj, lcls, loss])``; mean reduction, gains from ``model.hyp``, objectness
     target ``(1 - gr) + gr * giou`` with ``model.gr``.  CUDA fp32 raw heads go through the fused HIP kernels, with
     ``hyp['fl_gamma'] > 0`` through their focal form (engine/loss.py, csrc/loss.hip: same values, gradient written
-    directly); everything else runs the torch ops below."""
+    directly); everything else runs the torch ops below.
+
+    ``model.box_loss`` ('giou' when the model has none; 'diou' / 'ciou' are darknet's ``iou_loss`` of the YOLOv4 cfgs) selects the
+    ``bbox_iou`` measure of the box term and of the objectness target; ``hyp['label_smoothing']`` (0 when absent) is ``smooth_BCE``'s
+    eps.  CIoU of a prediction that equals its label exactly is nan here, the reference's arithmetic (alpha = 0 / 0); the fused
+    kernels take the limit there (include/yolo_hip.h)."""
+    kind = getattr(model, 'box_loss', 'giou')
+    if kind not in BOX_LOSSES:
+        raise ValueError('unknown box loss %r: expected one of %s' % (kind, ', '.join(BOX_LOSSES)))
     if fused is not False and (p[0].is_cuda or _fused_loss_override()):
         from engine import loss as hip_loss
         if hip_loss.usable(p, model):
@@ -252,7 +263,7 @@ def compute_loss(p, targets, model, fused=None):
     h = model.hyp
     bce_cls = nn.BCEWithLogitsLoss(pos_weight=torch.tensor([h['cls_pw']], device=dev), reduction='mean')
     bce_obj = nn.BCEWithLogitsLoss(pos_weight=torch.tensor([h['obj_pw']], device=dev), reduction='mean')
-    cp, cn = smooth_BCE(eps=0.0)
+    cp, cn = smooth_BCE(eps=h.get('label_smoothing', 0.0))
     if h['fl_gamma'] > 0:
         bce_cls, bce_obj = FocalLoss(bce_cls, h['fl_gamma']), FocalLoss(bce_obj, h['fl_gamma'])
     for i, pi in enumerate(p):
@@ -263,7 +274,7 @@ def compute_loss(p, targets, model, fused=None):
             ps = pi[b, a, gj, gi]
             pxy = torch.sigmoid(ps[:, 0:2])
             pwh = torch.exp(ps[:, 2:4]).clamp(max=1E3) * anchor_vec[i]
-            giou = bbox_iou(torch.cat((pxy, pwh), 1).t(), tbox[i], x1y1x2y2=False, GIoU=True)
+            giou = bbox_iou(torch.cat((pxy, pwh), 1).t(), tbox[i], x1y1x2y2=False, **{BOX_LOSSES[kind]: True})
             lbox = lbox + (1.0 - giou).mean()
             tobj[b, a, gj, gi] = (1.0 - model.gr) + model.gr * giou.detach().clamp(0).type(tobj.dtype)
             if model.nc > 1:

@@ -310,6 +310,24 @@ int yh_yolo_decode(const yh_decode_desc* d, void* stream);
  * d->io and d->raw are ignored; call once per head with the same cand / count buffers; cand == NULL counts only.            */
 int yh_yolo_decode_candidates(const yh_decode_desc* d, float conf_thres, int multi_label, const uint8_t* class_mask,
                               float* cand, int32_t* count, int cap, void* stream);
+/* darknet's scale_x_y ("grid sensitivity", the [yolo] key of the YOLOv4 cfgs): with s = scale_x_y and c = 0.5 * (s - 1) the centre is
+ *   xy = ((sigmoid(t) * s - c) + cell) * stride
+ * product, difference and sum rounded separately in fp32 - the host statement torch.sigmoid(t) * s - c + grid, never an fma.  The
+ * centre can reach and cross its cell's border by c.  Everything else is yh_yolo_decode's.  The descriptor embeds yh_decode_desc,
+ * whose layout does not change; s must be finite and in [1, 2] (darknet's cfgs use 1.05 .. 2.0), anything else is YH_EINVAL before
+ * any launch.  scale_x_y == 1 runs yh_yolo_decode's own kernels: the same bits.  Plans carry it as YH_OP_DECODE_SXY.
+ * yh_yolo_decode_candidates_sxy is the fused decode + candidate filter on that centre and covers yh_yolo_decode_candidates and its
+ * _tta form (below) in one entry: `scale` and `flip_w` are the _tta entry's, applied to the already scaled centre in models.py's order;
+ * scale == 1 with flip_w < 0 is the plain form.  Same records, same key contract; with scale_x_y == 1 the records of the entry it
+ * extends, bit for bit.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+typedef struct yh_decode_sxy_desc {
+    yh_decode_desc d;
+    float scale_x_y;
+} yh_decode_sxy_desc;
+int yh_yolo_decode_sxy(const yh_decode_sxy_desc* d, void* stream);
+int yh_yolo_decode_candidates_sxy(const yh_decode_sxy_desc* d, float scale, float flip_w, float conf_thres, int multi_label,
+                                  const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Non-maximum suppression, utils/utils.py:782-860, batched over the n images of one forward.
@@ -509,6 +527,15 @@ int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float alpha, void
 enum { YH_BOX_GIOU = 0, YH_BOX_DIOU = 1, YH_BOX_CIOU = 2 };
 int yh_yolo_loss_box_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream);
 int yh_yolo_loss_box_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream);
+/* The same with darknet's scale_x_y of the head (see yh_decode_sxy_desc): the loss statement's centre becomes
+ *   pxy = sigmoid(ps[:, 0:2]) * s - c,   c = 0.5 * (s - 1),   d pxy / dt = s * sig * (1 - sig)
+ * and everything downstream - pwh, the box measure, tobj, the assignment of a label to the cell that contains its centre - is
+ * unchanged; the assignment, objectness and dense-backward kernels are the ones of the entries above.  Validation is that of
+ * yh_yolo_loss_box_*; a scale_x_y that is not finite or outside [1, 2] is YH_EINVAL before any launch.  scale_x_y == 1 runs the
+ * kernels of yh_yolo_loss_box_*: the same bits.
+ * Added without a change of YH_ABI_VERSION: no struct or existing entry changed, a binding of ABI 2 that does not know it keeps working. */
+int yh_yolo_loss_head_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, float scale_x_y, void* stream);
+int yh_yolo_loss_head_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, float scale_x_y, void* stream);
 
 /* Backward of the depthwise block and of squeeze-excite (training of the Mobilenet / Ghost backbones).
  *  yh_dw_wgrad   dw[c][r][s] += sum_pixels dz[p][c] * x[p shifted by (r, s)][c]   (fp32 [c][k][k], caller zeroes)
@@ -1090,7 +1117,8 @@ enum { YH_OP_CONV = 1, YH_OP_STEM = 2, YH_OP_POOL = 3, YH_OP_COPY = 4, YH_OP_ADD
        YH_OP_SE = 8, YH_OP_QCOPY = 9, YH_OP_QPOOL = 10, YH_OP_QADD = 11, YH_OP_BN_STATS = 12, YH_OP_BN_FINALIZE = 13,
        YH_OP_BN_ACT_FWD = 14, YH_OP_BN_BWD_REDUCE = 15, YH_OP_BN_BWD_APPLY = 16, YH_OP_WGRAD = 17, YH_OP_STEM_WGRAD = 18,
        YH_OP_DILATE2 = 19, YH_OP_UPSAMPLE2_BWD = 20, YH_OP_CAST_F32 = 21, YH_OP_NCHW_TO_NHWC = 22, YH_OP_POOL_BWD = 23, YH_OP_PACK_BATCH = 24, YH_OP_DW_WGRAD = 25, YH_OP_DW_DGRAD = 26,
-       YH_OP_SE_BWD = 27, YH_OP_STEM_BWD = 28, YH_OP_QADD_CLAMPED = 29 /* yh_qadd_desc through yh_qadd_clamped */ };
+       YH_OP_SE_BWD = 27, YH_OP_STEM_BWD = 28, YH_OP_QADD_CLAMPED = 29 /* yh_qadd_desc through yh_qadd_clamped */,
+       YH_OP_DECODE_SXY = 30 /* yh_decode_sxy_desc through yh_yolo_decode_sxy */ };
 typedef struct yh_pack_batch_desc { const yh_pack_item* items; int32_t n_items; } yh_pack_batch_desc;
 typedef struct yh_layout_desc { const float* x; void* y; int32_t n, c, h, w_in, c_pad, ldy, dtype; } yh_layout_desc;
 

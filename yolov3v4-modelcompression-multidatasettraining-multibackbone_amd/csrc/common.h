@@ -305,6 +305,8 @@ inline hipError_t ensure_dynamic_lds(const void* kern, size_t bytes) {
 }
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+// darknet's scale_x_y as the *_sxy / yh_yolo_loss_head_* entries accept it: finite, 1 <= s <= 2 (a NaN fails both comparisons)
+inline bool yh_scale_xy_ok(float s) { return s >= 1.f && s <= 2.f; }
 
 // Weight-gradient reduce launches off the critical path (round 6, yh_plan_set_async_reduce).  A weight gradient is a split-K GEMM: the main
 // kernel leaves per-split partial tiles in the workspace and small HBM-bound launches add them into dW - which nothing reads before the

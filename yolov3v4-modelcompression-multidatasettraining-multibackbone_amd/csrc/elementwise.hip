@@ -307,8 +307,17 @@ __global__ __launch_bounds__(256) void add_gather_kernel(const yh_add_desc d) {
 // nx * no floats, contiguous in io and raw).  The (cell, anchor, channel) index of a thread advances by 256 elements per trip with
 // two carries instead of a division; one exponential per element (of v for w / h, of -v for the sigmoids); 4 independent loads per
 // trip, issued one trip ahead; 32-bit offsets.  Byte-bound by design: 4 B read + 4 B written per value, ~25 VALU slots per value.
-template <bool RAW>
-__global__ __launch_bounds__(256) void yolo_decode_kernel(const yh_decode_desc d) {
+// SXY: darknet's scale_x_y of the head (yh_decode_sxy_desc): the centre is (sigmoid * s - c) + grid, c = 0.5 (s - 1) taken on the host,
+// product and difference rounded separately as the host statement's two tensor operations (sxy_centre).  SXY = false compiles both out
+// and never reads the two arguments: the instantiations behind yh_yolo_decode are the ones this file had before the key existed.
+__device__ __forceinline__ float sxy_centre(float sg, float s, float c) {
+#pragma clang fp contract(off)
+    const float m = sg * s;
+    return m - c;
+}
+
+template <bool RAW, bool SXY>
+__global__ __launch_bounds__(256) void yolo_decode_kernel(const yh_decode_desc d, const float sxy, const float sxy_c) {
     __shared__ float anchor[16];
     if (threadIdx.x < 16) anchor[threadIdx.x] = threadIdx.x < 8 ? d.anchor_w[threadIdx.x & 7] : d.anchor_h[threadIdx.x & 7];
     __syncthreads();
@@ -337,7 +346,8 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const yh_decode_desc d
         const bool wh = oo == 2 || oo == 3;
         const float e = exp_fast(wh ? v : -v);
         const float sg = rcp_fast(1.f + e);
-        const float box = (sg + (oo == 0 ? (float)xx : fy)) * d.stride;                  // models.py:410-413: (sigmoid + grid) * stride
+        const float ctr = SXY ? sxy_centre(sg, sxy, sxy_c) : sg;
+        const float box = (ctr + (oo == 0 ? (float)xx : fy)) * d.stride;                 // models.py:410-413: (sigmoid + grid) * stride
         const float size = (e * anchor[(oo == 3 ? 8 : 0) + aa]) * d.stride;             // (exp * anchor) * stride
         return wh ? size : (oo < 2 ? box : sg);
     };
@@ -387,8 +397,8 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const yh_decode_desc d
 // channel) pair for the whole kernel - which of the three formulas applies, the anchor and the output run are per-thread constants -
 // and walks over the cells of the grid row, 256 / (na no) cells per pass.  Per value: one add for the source offset, one for the
 // destination, the exponential, the reciprocal, two selects.  Loads run one trip (U passes) ahead of the stores, as above.
-template <bool RAW>
-__global__ __launch_bounds__(256) void yolo_decode_cell_kernel(const yh_decode_desc d) {
+template <bool RAW, bool SXY>
+__global__ __launch_bounds__(256) void yolo_decode_cell_kernel(const yh_decode_desc d, const float sxy, const float sxy_c) {
     __shared__ float anchor[16];
     if (threadIdx.x < 16) anchor[threadIdx.x] = threadIdx.x < 8 ? d.anchor_w[threadIdx.x & 7] : d.anchor_h[threadIdx.x & 7];
     __syncthreads();
@@ -408,7 +418,8 @@ __global__ __launch_bounds__(256) void yolo_decode_cell_kernel(const yh_decode_d
     auto value = [&](float v, int x) {
         const float e = exp_fast(wh ? v : -v);
         const float sg = rcp_fast(1.f + e);
-        const float b = (sg + (o == 0 ? (float)x : fy)) * d.stride;       // models.py:410-413: (sigmoid + grid) * stride
+        const float ctr = SXY ? sxy_centre(sg, sxy, sxy_c) : sg;
+        const float b = (ctr + (o == 0 ? (float)x : fy)) * d.stride;      // models.py:410-413: (sigmoid + grid) * stride
         const float s = (e * anc) * d.stride;                            // (exp * anchor) * stride
         return wh ? s : (box ? b : sg);
     };
@@ -587,18 +598,29 @@ extern "C" int yh_add_channels(const yh_add_desc* d, void* stream) {
     return check_launch();
 }
 
-extern "C" int yh_yolo_decode(const yh_decode_desc* d, void* stream) {
+template <bool SXY>
+static int decode_launch(const yh_decode_desc* d, float sxy, void* stream) {
     if (!d || !d->p || !d->io || d->n <= 0 || d->ny <= 0 || d->nx <= 0 || d->na <= 0 || d->na > 8 || d->no < 5) return YH_EINVAL;
     if (d->ldp < d->na * d->no || d->row_off < 0 || d->row_off + d->na * d->ny * d->nx > d->rows_total) return YH_EINVAL;
     const long rows = (long)d->n * d->ny;
     if (rows > 0x7fffffffL || (long)d->nx * d->ldp > 0x3fffffffL || (long)d->na * d->ny * d->nx * d->no > 0x7fffffffL) return YH_EINVAL;
     static const bool generic = getenv("YH_DECODE_GENERIC") != nullptr;      // A/B: the element-order kernel for every head
+    const float c = 0.5f * (sxy - 1.f);
     if (d->na * d->no <= 256 && !generic) {
-        if (d->raw) hipLaunchKernelGGL(yolo_decode_cell_kernel<true>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d);
-        else hipLaunchKernelGGL(yolo_decode_cell_kernel<false>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d);
+        if (d->raw) hipLaunchKernelGGL((yolo_decode_cell_kernel<true, SXY>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d, sxy, c);
+        else hipLaunchKernelGGL((yolo_decode_cell_kernel<false, SXY>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d, sxy, c);
         return check_launch();
     }
-    if (d->raw) hipLaunchKernelGGL(yolo_decode_kernel<true>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d);
-    else hipLaunchKernelGGL(yolo_decode_kernel<false>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d);
+    if (d->raw) hipLaunchKernelGGL((yolo_decode_kernel<true, SXY>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d, sxy, c);
+    else hipLaunchKernelGGL((yolo_decode_kernel<false, SXY>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, *d, sxy, c);
     return check_launch();
+}
+
+extern "C" int yh_yolo_decode(const yh_decode_desc* d, void* stream) { return decode_launch<false>(d, 1.f, stream); }
+
+// scale_x_y == 1 is yh_yolo_decode itself (the same kernels: x * 1 - 0 would give the same bits, but nothing needs to rely on that)
+extern "C" int yh_yolo_decode_sxy(const yh_decode_sxy_desc* d, void* stream) {
+    if (!d || !yh_scale_xy_ok(d->scale_x_y)) return YH_EINVAL;
+    if (d->scale_x_y == 1.f) return decode_launch<false>(&d->d, 1.f, stream);
+    return decode_launch<true>(&d->d, d->scale_x_y, stream);
 }

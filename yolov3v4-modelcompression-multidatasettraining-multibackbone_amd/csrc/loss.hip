@@ -88,11 +88,17 @@ __device__ __forceinline__ Dual4 datan(const Dual4& a) {
 // alpha is a constant for the derivative (the statement's torch.no_grad()).  Where 1 - iou + v <= 0 - the prediction equals its label
 // exactly: iou == 1 and v == 0 in fp32 - alpha is 0, the limit of v * alpha; the statement divides 0 by 0 there and returns NaN for
 // value and gradient.  A NaN logit fails `<= 0` and propagates.
-template <int BOX>
-__device__ __forceinline__ Dual4 box_measure_of(const float* ps4, const float* an, const float* tb) {
+// SXY (darknet's scale_x_y, the yh_yolo_loss_head_* entries): pxy = sigmoid * s - c, c = 0.5 (s - 1), d pxy / dt = s * (sg * (1 - sg));
+// everything downstream is the same chain.  SXY = false is the code above without s and c: the instantiations behind the older entries.
+template <int BOX, bool SXY>
+__device__ __forceinline__ Dual4 box_measure_of(const float* ps4, const float* an, const float* tb, float s, float c) {
     Dual4 px = mk(sigmoidf(ps4[0])), py = mk(sigmoidf(ps4[1]));
     px.d[0] = px.v * (1.f - px.v);
     py.d[1] = py.v * (1.f - py.v);
+    if constexpr (SXY) {
+        px.v = px.v * s - c; px.d[0] = s * px.d[0];
+        py.v = py.v * s - c; py.d[1] = s * py.d[1];
+    }
     const float ew = expf(ps4[2]), eh = expf(ps4[3]);
     Dual4 pw = mk(fminf(ew, 1e3f) * an[0]), ph = mk(fminf(eh, 1e3f) * an[1]);
     pw.d[2] = ew < 1e3f ? pw.v : 0.f;                    // clamp(max=1e3) cuts the gradient
@@ -179,8 +185,9 @@ __global__ __launch_bounds__(256) void loss_assign_kernel(const yh_loss_desc d) 
 // candidate used to run inside one thread (80 dependent global loads + BCEs: 33 - 83 us for 1536 threads, latency bound); the thread
 // of class 0 also takes the box term.  nc == 1: one thread per candidate, no class term (as the reference, utils.py:412).
 // BOX selects the box measure (box_measure_of); it is the statement's one variable, so the objectness target takes it too.
-template <bool FOCAL, int BOX>
-__global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
+template <bool FOCAL, int BOX, bool SXY>
+__global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_desc d, const float gamma, const float alpha, const float sxy,
+                                                               const float sxy_c) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = idx / ncl, c = idx - k * ncl;
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(256) void loss_matched_fwd_kernel(const yh_loss_des
         const float* ps = d.p + m.b * d.sb + m.a * d.sa + m.gy * d.sy + m.gx * d.sx;
         if (c == 0) {
             const float box[4] = {ps[0], ps[1], ps[2], ps[3]};
-            const Dual4 g = box_measure_of<BOX>(box, m.an, m.tb);
+            const Dual4 g = box_measure_of<BOX, SXY>(box, m.an, m.tb, sxy, sxy_c);
             lbox = 1.f - g.v;
             if (d.winner[m.cell] == k) d.tobj[m.cell] = (1.f - d.gr) + d.gr * fmaxf(g.v, 0.f);
         }
@@ -277,8 +284,9 @@ __global__ __launch_bounds__(256) void loss_dense_bwd_kernel(const yh_loss_desc 
 
 // matched candidates, backward: box and class terms added on top of the dense pass (duplicates of a cell accumulate); one thread per
 // (candidate, class) as in the forward
-template <bool FOCAL, int BOX>
-__global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_desc d, const float gamma, const float alpha) {
+template <bool FOCAL, int BOX, bool SXY>
+__global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_desc d, const float gamma, const float alpha, const float sxy,
+                                                               const float sxy_c) {
     const int ncl = d.nc > 1 ? d.nc : 1;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int k = idx / ncl, c = idx - k * ncl;
@@ -290,7 +298,7 @@ __global__ __launch_bounds__(256) void loss_matched_bwd_kernel(const yh_loss_des
     if (c == 0) {
         const float w_box = *d.scale * d.g_box / (float)nb;
         const float box[4] = {ps[0], ps[1], ps[2], ps[3]};
-        const Dual4 g = box_measure_of<BOX>(box, m.an, m.tb);
+        const Dual4 g = box_measure_of<BOX, SXY>(box, m.an, m.tb, sxy, sxy_c);
 #pragma unroll
         for (int i = 0; i < 4; ++i) atomicAdd(gp + i, -w_box * g.d[i]);
     }
@@ -318,27 +326,27 @@ static int check_focal(float gamma, float alpha) {
     return YH_OK;
 }
 
-template <bool FOCAL, int BOX>
-static int loss_fwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
+template <bool FOCAL, int BOX, bool SXY = false>
+static int loss_fwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s, float sxy = 1.f) {
     if (d->nt > 0) {
         const unsigned blocks = (unsigned)(((long)d->na * d->nt + 255) / 256);
         const unsigned cblocks = (unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256);
         hipLaunchKernelGGL(loss_assign_kernel, dim3(blocks), dim3(256), 0, s, *d);
-        hipLaunchKernelGGL((loss_matched_fwd_kernel<FOCAL, BOX>), dim3(cblocks), dim3(256), 0, s, *d, gamma, alpha);
+        hipLaunchKernelGGL((loss_matched_fwd_kernel<FOCAL, BOX, SXY>), dim3(cblocks), dim3(256), 0, s, *d, gamma, alpha, sxy, 0.5f * (sxy - 1.f));
     }
     if ((long)d->bs * d->na * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
     hipLaunchKernelGGL((loss_obj_fwd_kernel<FOCAL>), dim3(grid_n((long)d->bs * d->na * d->ny * d->nx)), dim3(256), 0, s, *d, gamma, alpha);
     return check_launch();
 }
 
-template <bool FOCAL, int BOX>
-static int loss_bwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s) {
+template <bool FOCAL, int BOX, bool SXY = false>
+static int loss_bwd(const yh_loss_desc* d, float gamma, float alpha, hipStream_t s, float sxy = 1.f) {
     if ((long)d->bs * d->ny * d->nx >= 0x7fffffffL) return YH_EUNSUPPORTED;
     const long pixels = (long)d->bs * d->ny * d->nx;
     hipLaunchKernelGGL((loss_dense_bwd_kernel<FOCAL>), dim3((unsigned)(pixels < 16384 ? pixels : 16384)), dim3(256), 0, s, *d, gamma, alpha);
     if (d->nt > 0)
-        hipLaunchKernelGGL((loss_matched_bwd_kernel<FOCAL, BOX>), dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)),
-                           dim3(256), 0, s, *d, gamma, alpha);
+        hipLaunchKernelGGL((loss_matched_bwd_kernel<FOCAL, BOX, SXY>), dim3((unsigned)(((long)d->na * d->nt * (d->nc > 1 ? d->nc : 1) + 255) / 256)),
+                           dim3(256), 0, s, *d, gamma, alpha, sxy, 0.5f * (sxy - 1.f));
     return check_launch();
 }
 
@@ -348,20 +356,28 @@ static int check_box(int box, float gamma, float alpha) {
     return gamma > 0.f ? check_focal(gamma, alpha) : YH_OK;
 }
 
-template <int BOX>
-static int loss_box(const yh_loss_desc* d, bool bwd, float gamma, float alpha, hipStream_t s) {
-    if (gamma > 0.f) return bwd ? loss_bwd<true, BOX>(d, gamma, alpha, s) : loss_fwd<true, BOX>(d, gamma, alpha, s);
-    return bwd ? loss_bwd<false, BOX>(d, 0.f, 0.f, s) : loss_fwd<false, BOX>(d, 0.f, 0.f, s);
+template <int BOX, bool SXY>
+static int loss_box(const yh_loss_desc* d, bool bwd, float gamma, float alpha, hipStream_t s, float sxy) {
+    if (gamma > 0.f) return bwd ? loss_bwd<true, BOX, SXY>(d, gamma, alpha, s, sxy) : loss_fwd<true, BOX, SXY>(d, gamma, alpha, s, sxy);
+    return bwd ? loss_bwd<false, BOX, SXY>(d, 0.f, 0.f, s, sxy) : loss_fwd<false, BOX, SXY>(d, 0.f, 0.f, s, sxy);
 }
 
-static int loss_box_entry(const yh_loss_desc* d, bool bwd, int box, float gamma, float alpha, void* stream) {
+// the yh_yolo_loss_head_* entries add scale_x_y, finite and in [1, 2]; 1 takes the instantiations of the yh_yolo_loss_box_* entries
+template <bool SXY>
+static int loss_box_kind(const yh_loss_desc* d, bool bwd, int box, float gamma, float alpha, hipStream_t s, float sxy) {
+    if (box == YH_BOX_DIOU) return loss_box<YH_BOX_DIOU, SXY>(d, bwd, gamma, alpha, s, sxy);
+    if (box == YH_BOX_CIOU) return loss_box<YH_BOX_CIOU, SXY>(d, bwd, gamma, alpha, s, sxy);
+    return loss_box<YH_BOX_GIOU, SXY>(d, bwd, gamma, alpha, s, sxy);
+}
+
+static int loss_box_entry(const yh_loss_desc* d, bool bwd, int box, float gamma, float alpha, float sxy, void* stream) {
     int rc = check_loss(d, bwd);
     if (!rc) rc = check_box(box, gamma, alpha);
+    if (!rc && !yh_scale_xy_ok(sxy)) rc = YH_EINVAL;
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (box == YH_BOX_DIOU) return loss_box<YH_BOX_DIOU>(d, bwd, gamma, alpha, s);
-    if (box == YH_BOX_CIOU) return loss_box<YH_BOX_CIOU>(d, bwd, gamma, alpha, s);
-    return loss_box<YH_BOX_GIOU>(d, bwd, gamma, alpha, s);
+    if (sxy == 1.f) return loss_box_kind<false>(d, bwd, box, gamma, alpha, s, 1.f);
+    return loss_box_kind<true>(d, bwd, box, gamma, alpha, s, sxy);
 }
 
 }  // namespace yh
@@ -395,9 +411,17 @@ extern "C" int yh_yolo_loss_focal_bwd(const yh_loss_desc* d, float gamma, float 
 }
 
 extern "C" int yh_yolo_loss_box_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream) {
-    return loss_box_entry(d, false, box, gamma, alpha, stream);
+    return loss_box_entry(d, false, box, gamma, alpha, 1.f, stream);
 }
 
 extern "C" int yh_yolo_loss_box_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, void* stream) {
-    return loss_box_entry(d, true, box, gamma, alpha, stream);
+    return loss_box_entry(d, true, box, gamma, alpha, 1.f, stream);
+}
+
+extern "C" int yh_yolo_loss_head_fwd(const yh_loss_desc* d, int box, float gamma, float alpha, float scale_x_y, void* stream) {
+    return loss_box_entry(d, false, box, gamma, alpha, scale_x_y, stream);
+}
+
+extern "C" int yh_yolo_loss_head_bwd(const yh_loss_desc* d, int box, float gamma, float alpha, float scale_x_y, void* stream) {
+    return loss_box_entry(d, true, box, gamma, alpha, scale_x_y, stream);
 }

@@ -125,11 +125,14 @@ __device__ __forceinline__ float dec_sigmoid(float v) { return rcp_fast(1.f + ex
 // decode and filter - cx, cy, w, h divided by the view's scale (IEEE fp32 division, as the reference's CPU `/=`), cx mirrored about
 // the ORIGINAL frame width when flip_w >= 0 (models.py:493-495) - so the (n, rows, 5 + nc) tensors of the three passes and their
 // torch.cat are never written either.  TTA = false compiles the two operations out: the plain entry's records do not change by a bit.
-template <bool ML, bool TTA>
+// SXY (darknet's scale_x_y, yh_yolo_decode_candidates_sxy): the centre is (sigmoid * s - c) + cell as in the decode kernels' SXY form -
+// two roundings, this file is compiled without contraction - and the de-augmentation acts on that centre, in models.py's order.
+// SXY = false compiles it out and never reads sxy / sxy_c.
+template <bool ML, bool TTA, bool SXY>
 __global__ __launch_bounds__(256) void yolo_decode_candidates_kernel(const yh_decode_desc d, const float conf,
                                                                      const uint8_t* __restrict__ class_mask, float* cand,
                                                                      int32_t* count, const int cap, const float scale,
-                                                                     const float flip_w) {
+                                                                     const float flip_w, const float sxy, const float sxy_c) {
     __shared__ float anchor[16];
     if (threadIdx.x < 16) anchor[threadIdx.x] = threadIdx.x < 8 ? d.anchor_w[threadIdx.x & 7] : d.anchor_h[threadIdx.x & 7];
     __syncthreads();
@@ -150,7 +153,11 @@ __global__ __launch_bounds__(256) void yolo_decode_candidates_kernel(const yh_de
         if (__ballot(live) == 0ull) continue;                // wave-uniform: emit() needs every lane of a wave
         float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
         if (live) {
-            float cx = (dec_sigmoid(src[0]) + (float)x) * d.stride, cy = (dec_sigmoid(src[1]) + (float)y) * d.stride;
+            float sx = dec_sigmoid(src[0]), sy = dec_sigmoid(src[1]);
+            if constexpr (SXY) {
+                sx = sx * sxy - sxy_c; sy = sy * sxy - sxy_c;
+            }
+            float cx = (sx + (float)x) * d.stride, cy = (sy + (float)y) * d.stride;
             float w = (exp_fast(src[2]) * anchor[a]) * d.stride, h = (exp_fast(src[3]) * anchor[8 + a]) * d.stride;
             if constexpr (TTA) {
                 cx = cx / scale; cy = cy / scale; w = w / scale; h = h / scale;
@@ -697,39 +704,47 @@ extern "C" int yh_nms_candidates(const float* pred, int n, int rows, int nc, flo
     return check_launch();
 }
 
-extern "C" int yh_yolo_decode_candidates(const yh_decode_desc* d, float conf_thres, int multi_label, const uint8_t* class_mask,
-                                         float* cand, int32_t* count, int cap, void* stream) {
+template <bool TTA, bool SXY>
+static int decode_candidates_launch(const yh_decode_desc* d, float scale, float flip_w, float sxy, float conf_thres, int multi_label,
+                                    const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream) {
     if (!d || !d->p || !count || d->n <= 0 || d->ny <= 0 || d->nx <= 0 || d->na <= 0 || d->na > 8 || d->no <= 5 || cap < 0) return YH_EINVAL;
+    if (TTA && (!(scale > 0.f) || flip_w != flip_w)) return YH_EINVAL;
     if (cand && !aligned16(cand)) return YH_EALIGN;
     if ((long)d->rows_total * (d->no - 5) > 0x7fffffffL) return YH_EUNSUPPORTED;      // the key is a 32-bit row * nc + cls
     const long total = (long)d->n * d->na * d->ny * d->nx;
     long g = (total + 255) / 256;
     if (g > 65536) g = 65536;
+    const float c = 0.5f * (sxy - 1.f);
     if (multi_label)
-        hipLaunchKernelGGL((yolo_decode_candidates_kernel<true, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
-                           conf_thres, class_mask, cand, count, cap, 1.f, -1.f);
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<true, TTA, SXY>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, scale, flip_w, sxy, c);
     else
-        hipLaunchKernelGGL((yolo_decode_candidates_kernel<false, false>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
-                           conf_thres, class_mask, cand, count, cap, 1.f, -1.f);
+        hipLaunchKernelGGL((yolo_decode_candidates_kernel<false, TTA, SXY>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
+                           conf_thres, class_mask, cand, count, cap, scale, flip_w, sxy, c);
     return check_launch();
+}
+
+extern "C" int yh_yolo_decode_candidates(const yh_decode_desc* d, float conf_thres, int multi_label, const uint8_t* class_mask,
+                                         float* cand, int32_t* count, int cap, void* stream) {
+    return decode_candidates_launch<false, false>(d, 1.f, -1.f, 1.f, conf_thres, multi_label, class_mask, cand, count, cap, stream);
 }
 
 extern "C" int yh_yolo_decode_candidates_tta(const yh_decode_desc* d, float scale, float flip_w, float conf_thres, int multi_label,
                                              const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream) {
-    if (!d || !d->p || !count || d->n <= 0 || d->ny <= 0 || d->nx <= 0 || d->na <= 0 || d->na > 8 || d->no <= 5 || cap < 0) return YH_EINVAL;
-    if (!(scale > 0.f) || flip_w != flip_w) return YH_EINVAL;
-    if (cand && !aligned16(cand)) return YH_EALIGN;
-    if ((long)d->rows_total * (d->no - 5) > 0x7fffffffL) return YH_EUNSUPPORTED;      // the key is a 32-bit row * nc + cls
-    const long total = (long)d->n * d->na * d->ny * d->nx;
-    long g = (total + 255) / 256;
-    if (g > 65536) g = 65536;
-    if (multi_label)
-        hipLaunchKernelGGL((yolo_decode_candidates_kernel<true, true>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
-                           conf_thres, class_mask, cand, count, cap, scale, flip_w);
-    else
-        hipLaunchKernelGGL((yolo_decode_candidates_kernel<false, true>), dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, *d,
-                           conf_thres, class_mask, cand, count, cap, scale, flip_w);
-    return check_launch();
+    return decode_candidates_launch<true, false>(d, scale, flip_w, 1.f, conf_thres, multi_label, class_mask, cand, count, cap, stream);
+}
+
+// One entry for the plain and the TTA form: scale == 1 and flip_w < 0 is the plain one (x / 1 is x), scale_x_y == 1 the unscaled kernels.
+extern "C" int yh_yolo_decode_candidates_sxy(const yh_decode_sxy_desc* d, float scale, float flip_w, float conf_thres, int multi_label,
+                                             const uint8_t* class_mask, float* cand, int32_t* count, int cap, void* stream) {
+    if (!d || !yh_scale_xy_ok(d->scale_x_y) || !(scale > 0.f) || flip_w != flip_w) return YH_EINVAL;
+    const bool tta = !(scale == 1.f && flip_w < 0.f);
+    const float s = d->scale_x_y;
+    if (s == 1.f)
+        return tta ? decode_candidates_launch<true, false>(&d->d, scale, flip_w, 1.f, conf_thres, multi_label, class_mask, cand, count, cap, stream)
+                   : decode_candidates_launch<false, false>(&d->d, 1.f, -1.f, 1.f, conf_thres, multi_label, class_mask, cand, count, cap, stream);
+    return tta ? decode_candidates_launch<true, true>(&d->d, scale, flip_w, s, conf_thres, multi_label, class_mask, cand, count, cap, stream)
+               : decode_candidates_launch<false, true>(&d->d, 1.f, -1.f, s, conf_thres, multi_label, class_mask, cand, count, cap, stream);
 }
 
 extern "C" int yh_nms_sort(const float* cand, const int32_t* count, int n, int cap, int mmax, float* sorted, void* stream) {

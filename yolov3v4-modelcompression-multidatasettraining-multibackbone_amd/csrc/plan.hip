@@ -21,6 +21,7 @@ union AnyDesc {
     yh_copy_desc copy;
     yh_add_desc add;
     yh_decode_desc decode;
+    yh_decode_sxy_desc decode_sxy;
     yh_dw_desc dw;
     yh_se_desc se;
     yh_qcopy_desc qcopy;
@@ -60,6 +61,7 @@ size_t desc_size(int kind) {
         case YH_OP_COPY: return sizeof(yh_copy_desc);
         case YH_OP_ADD: return sizeof(yh_add_desc);
         case YH_OP_DECODE: return sizeof(yh_decode_desc);
+        case YH_OP_DECODE_SXY: return sizeof(yh_decode_sxy_desc);
         case YH_OP_DW: return sizeof(yh_dw_desc);
         case YH_OP_SE: return sizeof(yh_se_desc);
         case YH_OP_QCOPY: return sizeof(yh_qcopy_desc);
@@ -88,6 +90,7 @@ int launch(int kind, const AnyDesc& d, void* stream) {
         case YH_OP_COPY: return yh_copy_channels(&d.copy, stream);
         case YH_OP_ADD: return yh_add_channels(&d.add, stream);
         case YH_OP_DECODE: return yh_yolo_decode(&d.decode, stream);
+        case YH_OP_DECODE_SXY: return yh_yolo_decode_sxy(&d.decode_sxy, stream);
         case YH_OP_DW: return yh_dwconv2d_fwd(&d.dw, stream);
         case YH_OP_SE: return yh_se_fwd(&d.se, stream);
         case YH_OP_QCOPY: return yh_qcopy(&d.qcopy, stream);

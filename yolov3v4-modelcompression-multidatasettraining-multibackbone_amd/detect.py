@@ -32,7 +32,8 @@ def detect(opt, save_img=True):
 
     model = Darknet(opt.cfg, imgsz, quantized=opt.quantized, quantizer_output=opt.quantizer_output, layer_idx=opt.layer_idx,
                     reorder=opt.reorder, TN=opt.TN, TM=opt.TM, a_bit=opt.a_bit, w_bit=opt.w_bit, FPGA=opt.FPGA,
-                    is_gray_scale=opt.gray_scale, maxabsscaler=opt.maxabsscaler, shortcut_way=opt.shortcut_way)
+                    is_gray_scale=opt.gray_scale, maxabsscaler=opt.maxabsscaler, shortcut_way=opt.shortcut_way,
+                    scale_x_y=getattr(opt, 'scale_x_y', False))
     if weights:
         attempt_download(weights)
         if weights.endswith('.pt'):
@@ -130,6 +131,10 @@ def make_parser():
     parser.add_argument('--classes', nargs='+', type=int, help='filter by class')
     parser.add_argument('--agnostic-nms', action='store_true', help='class-agnostic NMS')
     parser.add_argument('--augment', action='store_true', help='augmented inference')
+    parser.add_argument('--scale-x-y', action='store_true',
+                        help="honour the scale_x_y key of the cfg's [yolo] sections (YOLOv4's grid sensitivity: box centre = sigmoid * s - "
+                             '(s - 1) / 2, 1.2 / 1.1 / 1.05 on the YOLOv4 heads) in decode and NMS filter.  Off by default: the reference '
+                             'ignores the key')
     parser.add_argument('--quantized', type=int, default=-1, help='quantization way')
     parser.add_argument('--shortcut_way', type=int, default=1, help='--shortcut quantization way')
     parser.add_argument('--a_bit', type=int, default=8, help='a-bit')

@@ -66,6 +66,16 @@ class DecodeDesc(C.Structure):
                 ('anchor_w', _f32 * 8), ('anchor_h', _f32 * 8)]
 
 
+class DecodeSxyDesc(C.Structure):
+    """yh_decode_sxy_desc: yh_decode_desc at offset 0 (the fixups of DecodeDesc's fields apply unchanged) and the head's scale_x_y."""
+    _fields_ = [('d', DecodeDesc), ('scale_x_y', _f32)]
+
+
+def decode_base(desc):
+    """The yh_decode_desc inside a decode descriptor of either kind (a view: writes land in ``desc``)."""
+    return desc.d if isinstance(desc, DecodeSxyDesc) else desc
+
+
 class DwDesc(C.Structure):
     _fields_ = [('x', _vp), ('w', _vp), ('bias', _vp), ('y', _vp),
                 ('n', _i32), ('h', _i32), ('w_in', _i32), ('c', _i32), ('ho', _i32), ('wo', _i32), ('k', _i32),
@@ -292,6 +302,7 @@ OP_BN_STATS, OP_BN_FINALIZE, OP_BN_ACT_FWD, OP_BN_BWD_REDUCE, OP_BN_BWD_APPLY = 
 OP_WGRAD, OP_STEM_WGRAD, OP_DILATE2, OP_UPSAMPLE2_BWD, OP_CAST_F32, OP_NCHW_TO_NHWC, OP_POOL_BWD, OP_PACK_BATCH = 17, 18, 19, 20, 21, 22, 23, 24
 OP_DW_WGRAD, OP_DW_DGRAD, OP_SE_BWD, OP_STEM_BWD = 25, 26, 27, 28
 OP_QADD_CLAMPED = 29
+OP_DECODE_SXY = 30
 
 OP_KIND = {BnStatsDesc: OP_BN_STATS, BnFinalizeDesc: OP_BN_FINALIZE, BnActFwdDesc: OP_BN_ACT_FWD,
            BnBwdReduceDesc: OP_BN_BWD_REDUCE, BnBwdApplyDesc: OP_BN_BWD_APPLY, WgradDesc: OP_WGRAD,
@@ -299,7 +310,7 @@ OP_KIND = {BnStatsDesc: OP_BN_STATS, BnFinalizeDesc: OP_BN_FINALIZE, BnActFwdDes
            SeBwdDesc: OP_SE_BWD, StemBwdDesc: OP_STEM_BWD,
            ConvDesc: OP_CONV, StemDesc: OP_STEM, PoolDesc: OP_POOL, CopyDesc: OP_COPY, AddDesc: OP_ADD,
            DecodeDesc: OP_DECODE, DwDesc: OP_DW, SeDesc: OP_SE, QCopyDesc: OP_QCOPY, QPoolDesc: OP_QPOOL, QAddDesc: OP_QADD,
-           QAddClampedDesc: OP_QADD_CLAMPED}
+           QAddClampedDesc: OP_QADD_CLAMPED, DecodeSxyDesc: OP_DECODE_SXY}
 
 _SIGNATURES = {
     'yh_abi_version': (C.c_int, []),
@@ -329,6 +340,8 @@ _SIGNATURES = {
     'yh_add_channels': (C.c_int, [C.POINTER(AddDesc), _vp]),
     'yh_yolo_decode': (C.c_int, [C.POINTER(DecodeDesc), _vp]),
     'yh_yolo_decode_candidates': (C.c_int, [C.POINTER(DecodeDesc), _f32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    'yh_yolo_decode_sxy': (C.c_int, [C.POINTER(DecodeSxyDesc), _vp]),
+    'yh_yolo_decode_candidates_sxy': (C.c_int, [C.POINTER(DecodeSxyDesc), _f32, _f32, _f32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     'yh_nms_candidates': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f32, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     'yh_nms_sort': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'yh_nms_sort_cls': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
@@ -376,6 +389,8 @@ _SIGNATURES = {
     'yh_yolo_loss_focal_bwd': (C.c_int, [C.POINTER(LossDesc), _f32, _f32, _vp]),
     'yh_yolo_loss_box_fwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _vp]),
     'yh_yolo_loss_box_bwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _vp]),
+    'yh_yolo_loss_head_fwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _f32, _vp]),
+    'yh_yolo_loss_head_bwd': (C.c_int, [C.POINTER(LossDesc), C.c_int, _f32, _f32, _f32, _vp]),
     'yh_nchw_to_nhwc': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'yh_letterbox_fwd': (C.c_int, [C.POINTER(LetterboxDesc), _vp]),
     'yh_resize_bilinear': (C.c_int, [C.POINTER(ResizeDesc), _vp]),

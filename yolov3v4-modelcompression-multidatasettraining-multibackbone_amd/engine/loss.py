@@ -23,6 +23,11 @@ without the focal element.  GIoU keeps the entries above.  ``YOLO_HIP_BOX_LOSS=0
 runs); ``box_stats()`` counts the calls.  Where a prediction equals its label exactly the CIoU kernels take ``alpha = 0`` and stay
 finite; the torch statement returns nan there (include/yolo_hip.h).  ``hyp['label_smoothing']`` only changes the two
 class targets ``cp`` / ``cn`` of the descriptor, so it never leaves the fused path.
+
+A head whose yolo module has ``scale_x_y != 1`` (darknet's grid sensitivity, ``Darknet(scale_x_y=True)``, ``--scale-x-y``) goes
+through ``yh_yolo_loss_head_fwd`` / ``_bwd``: the matched kernels with ``pxy = sigmoid * s - 0.5 (s - 1)`` and its derivative, any box
+kind, with or without the focal element; the other heads of the model keep the entries above.  ``YOLO_HIP_SCALE_XY=0`` keeps the
+torch statement for a model with such a head (A/B runs); ``scale_stats()`` counts the calls.
 """
 import ctypes as C
 import os
@@ -37,6 +42,7 @@ FOCAL_ALPHA = 0.25     # utils.utils.compute_loss builds FocalLoss(bce, fl_gamma
 _STATS = dict(focal_fwd=0, focal_bwd=0)
 BOX_KINDS = {'giou': 0, 'diou': 1, 'ciou': 2}      # YH_BOX_* of include/yolo_hip.h
 _BOX_STATS = dict(box_fwd=0, box_bwd=0)
+_SCALE_STATS = dict(scale_fwd=0, scale_bwd=0)
 
 
 def _lib():
@@ -63,6 +69,21 @@ def reset_box_stats():
         _BOX_STATS[k] = 0
 
 
+def scale_stats():
+    """Counters since ``reset_scale_stats``: calls of ``yh_yolo_loss_head_fwd`` / ``_bwd`` (one per scaled head and pass)."""
+    return dict(_SCALE_STATS)
+
+
+def reset_scale_stats():
+    for k in _SCALE_STATS:
+        _SCALE_STATS[k] = 0
+
+
+def head_scales(model, yolo_modules):
+    """``scale_x_y`` of the model's yolo modules in head order (1.0 for a module without the attribute)."""
+    return [float(getattr(layer, 'scale_x_y', 1.0)) for layer in yolo_modules(model)]
+
+
 def box_kind(model):
     """``model.box_loss`` ('giou' when the model has none) as YH_BOX_*; an unknown kind raises ValueError naming it."""
     kind = getattr(model, 'box_loss', 'giou')
@@ -71,14 +92,17 @@ def box_kind(model):
     return BOX_KINDS[kind]
 
 
-def usable(p, model):
+def usable(p, model, scaled=False):
     """Fused path: CUDA (or an injected emulator), fp32 raw heads with unit stride on the last axis; focal loss too unless
-    ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for it, DIoU / CIoU too unless ``YOLO_HIP_BOX_LOSS=0`` does."""
+    ``YOLO_HIP_FOCAL_LOSS=0`` keeps the torch statement for it, DIoU / CIoU too unless ``YOLO_HIP_BOX_LOSS=0`` does, a head with
+    ``scale_x_y != 1`` (``scaled``) too unless ``YOLO_HIP_SCALE_XY=0`` does."""
     if _LIB_OVERRIDE is None and not p[0].is_cuda:
         return False
     if model.hyp.get('fl_gamma', 0.0) > 0 and os.environ.get('YOLO_HIP_FOCAL_LOSS', '1') == '0':
         return False
     if box_kind(model) != BOX_KINDS['giou'] and os.environ.get('YOLO_HIP_BOX_LOSS', '1') == '0':
+        return False
+    if scaled and os.environ.get('YOLO_HIP_SCALE_XY', '1') == '0':
         return False
     return all(t.dtype == torch.float32 and t.dim() == 5 and t.stride(4) == 1 for t in p)
 
@@ -148,7 +172,13 @@ class _YoloLoss(torch.autograd.Function):
                          bs=bs, na=na, ny=ny, nx=nx, no=no, nc=no - 5, nt=nt, iou_t=meta['iou_t'], gr=meta['gr'],
                          cp=meta['cp'], cn=meta['cn'], cls_pw=meta['cls_pw'], obj_pw=meta['obj_pw'],
                          g_box=meta['giou'], g_obj=meta['obj'], g_cls=meta['cls'])
-            if meta['box']:
+            if meta['sxy'][i] != 1.0:
+                hiplib.check(lib.yh_yolo_loss_head_fwd(C.byref(d), meta['box'], meta['gamma'], meta['alpha'], meta['sxy'][i],
+                                                       hiplib.stream_ptr()), 'yh_yolo_loss_head_fwd')
+                _SCALE_STATS['scale_fwd'] += 1
+                _BOX_STATS['box_fwd'] += meta['box'] > 0
+                _STATS['focal_fwd'] += meta['gamma'] > 0
+            elif meta['box']:
                 hiplib.check(lib.yh_yolo_loss_box_fwd(C.byref(d), meta['box'], meta['gamma'], meta['alpha'], hiplib.stream_ptr()), 'yh_yolo_loss_box_fwd')
                 _BOX_STATS['box_fwd'] += 1
                 _STATS['focal_fwd'] += meta['gamma'] > 0
@@ -157,7 +187,7 @@ class _YoloLoss(torch.autograd.Function):
                 _STATS['focal_fwd'] += 1
             else:
                 hiplib.check(lib.yh_yolo_loss_fwd(C.byref(d), hiplib.stream_ptr()), 'yh_yolo_loss_fwd')
-            heads.append((d, tobj, p))
+            heads.append((d, tobj, p, meta['sxy'][i]))
             cells.append(float(bs * na * ny * nx))
             del winner   # only the forward needs it (stream-ordered free)
         nc = ps[0].shape[4] - 5
@@ -188,7 +218,7 @@ class _YoloLoss(torch.autograd.Function):
         scale = g_loss.detach().float().contiguous().reshape(1)
         gamma, alpha = ctx.focal
         grads = []
-        for d, tobj, p in ctx.heads:
+        for d, tobj, p, sxy in ctx.heads:
             if ctx.on_bases:
                 bs, na, ny, nx, no = p.shape
                 ld = p.stride(3)
@@ -201,7 +231,12 @@ class _YoloLoss(torch.autograd.Function):
             d.grad, d.scale = hiplib.ptr(g), hiplib.ptr(scale)
             d.gb, d.ga, d.gy, d.gx = g.stride(0), g.stride(1), g.stride(2), g.stride(3)
             with hiplib.on_device(p):
-                if ctx.box:
+                if sxy != 1.0:
+                    hiplib.check(lib.yh_yolo_loss_head_bwd(C.byref(d), ctx.box, gamma, alpha, sxy, hiplib.stream_ptr()), 'yh_yolo_loss_head_bwd')
+                    _SCALE_STATS['scale_bwd'] += 1
+                    _BOX_STATS['box_bwd'] += ctx.box > 0
+                    _STATS['focal_bwd'] += gamma > 0
+                elif ctx.box:
                     hiplib.check(lib.yh_yolo_loss_box_bwd(C.byref(d), ctx.box, gamma, alpha, hiplib.stream_ptr()), 'yh_yolo_loss_box_bwd')
                     _BOX_STATS['box_bwd'] += 1
                     _STATS['focal_bwd'] += gamma > 0
@@ -225,7 +260,8 @@ def compute_loss(p, targets, model, yolo_modules, smooth_bce):
     meta = dict(targets=targets.to(device=dev, dtype=torch.float32).contiguous(), anchors=anchors, iou_t=float(h['iou_t']),
                 gr=float(model.gr), cp=float(cp), cn=float(cn), cls_pw=float(h['cls_pw']),
                 obj_pw=float(h['obj_pw']), giou=float(h['giou']), obj=float(h['obj']), cls=float(h['cls']),
-                gamma=float(h.get('fl_gamma', 0.0)), alpha=FOCAL_ALPHA, box=box_kind(model))
+                gamma=float(h.get('fl_gamma', 0.0)), alpha=FOCAL_ALPHA, box=box_kind(model),
+                sxy=head_scales(model, yolo_modules))
     bases = _head_bases(p)
     with hiplib.on_device(p[0]):
         if bases is not None:

@@ -62,13 +62,19 @@ class _Rows:
 class _Heads:
     """... or the head convolutions' outputs themselves (yh_yolo_decode_candidates: decode and filter in one pass, DarknetEngine.detect).
     An entry is a descriptor, or ``(descriptor, scale, flip_w)`` for the head of an augmented view whose rows are mapped back to the
-    frame inside the pass (yh_yolo_decode_candidates_tta, DarknetEngine.detect with ``augment``)."""
+    frame inside the pass (yh_yolo_decode_candidates_tta, DarknetEngine.detect with ``augment``).  A head with darknet's scale_x_y is a
+    ``DecodeSxyDesc`` and goes through yh_yolo_decode_candidates_sxy, which covers both forms."""
 
     def __init__(self, descs, n, rows, nc, device):
         self.descs, self.n, self.rows, self.nc, self.device = descs, n, rows, nc, device
 
     def candidates(self, lib, conf, ml, cmask, cand, count, cap, stream):
         for d in self.descs:
+            if isinstance(d[0] if isinstance(d, tuple) else d, hiplib.DecodeSxyDesc):
+                d, scale, flip_w = d if isinstance(d, tuple) else (d, 1.0, -1.0)
+                hiplib.check(lib.yh_yolo_decode_candidates_sxy(C.byref(d), scale, flip_w, conf, ml, hiplib.ptr(cmask), hiplib.ptr(cand),
+                                                               hiplib.ptr(count), cap, stream), 'scaled decode + candidates')
+                continue
             if isinstance(d, tuple):
                 d, scale, flip_w = d
                 hiplib.check(lib.yh_yolo_decode_candidates_tta(C.byref(d), scale, flip_w, conf, ml, hiplib.ptr(cmask), hiplib.ptr(cand),
@@ -80,11 +86,12 @@ class _Heads:
     def images(self, i0, i1):
         part = []
         for entry in self.descs:
-            d = entry[0] if isinstance(entry, tuple) else entry
-            e = hiplib.DecodeDesc.from_buffer_copy(d)
+            desc = entry[0] if isinstance(entry, tuple) else entry
+            copy = type(desc).from_buffer_copy(desc)
+            d, e = hiplib.decode_base(desc), hiplib.decode_base(copy)
             e.p = d.p + i0 * d.ny * d.nx * d.ldp * 4          # fp32 NHWC with pitch ldp, image-major
             e.n = i1 - i0
-            part.append((e,) + entry[1:] if isinstance(entry, tuple) else e)
+            part.append((copy,) + entry[1:] if isinstance(entry, tuple) else copy)
         return _Heads(part, i1 - i0, self.rows, self.nc, self.device)
 
 

@@ -102,6 +102,7 @@ class Head:
         self.block, self.src = block, src
         self.na, self.no, self.nc = module.na, module.no, module.nc
         self.stride = float(module.stride)
+        self.scale_x_y = float(getattr(module, 'scale_x_y', 1.0))      # darknet's grid sensitivity; 1.0 unless Darknet(scale_x_y=True)
         self.anchor_vec = module.anchor_vec.detach().float().cpu().numpy()  # anchors / stride, fp32 (models.py:362)
 
 
@@ -858,11 +859,13 @@ class DarknetEngine:
             for a in range(h.na):
                 d.anchor_w[a] = float(h.anchor_vec[a, 0])
                 d.anchor_h[a] = float(h.anchor_vec[a, 1])
+            if h.scale_x_y != 1.0:      # a scaled head is YH_OP_DECODE_SXY; an unscaled one keeps the op and the entry it always had
+                d = hiplib.DecodeSxyDesc(d=d, scale_x_y=h.scale_x_y)
             op = add(d, 'yolo%d' % h.block)
-            fixup(op, DecodeDesc, 'io', SLOT_IO)
+            fixup(op, DecodeDesc, 'io', SLOT_IO)              # yh_decode_desc sits at offset 0 of yh_decode_sxy_desc
             fixup(op, DecodeDesc, 'raw', SLOT_RAW0 + k)      # bound to NULL per call when the caller does not want the copies
             plan['raw_shapes'].append((N, h.na, s.H, s.W, h.no))
-            plan['decode_descs'].append(DecodeDesc.from_buffer_copy(d))
+            plan['decode_descs'].append(type(d).from_buffer_copy(d))
             off += h.na * s.H * s.W
         plan['rows'], plan['no'] = rows, no
         return plan
@@ -917,7 +920,7 @@ class DarknetEngine:
         N = x.shape[0]
         lib, handle = self.lib, plan['handle']
         if (0 < N <= self.graph_max_batch and x.is_cuda and hasattr(lib, 'yh_plan_graph_launch')) or self.return_features \
-                or os.environ.get('YOLO_HIP_FUSED_DETECT', '1') == '0':
+                or os.environ.get('YOLO_HIP_FUSED_DETECT', '1') == '0' or self._scaled_two_pass(plan):
             keep = self.want_raw
             self.want_raw = False
             try:
@@ -929,6 +932,15 @@ class DarknetEngine:
         hiplib.check(lib.yh_plan_run_range(handle, 0, plan['first_decode_op'], hiplib.stream_ptr()), 'yh_plan_run_range')
         return hnms.non_max_suppression_heads(plan['decode_descs'], N, plan['rows'], plan['no'] - 5, x.device, conf_thres, iou_thres,
                                               multi_label, classes, agnostic)
+
+    def _scaled_two_pass(self, plan):
+        """``YOLO_HIP_SCALE_XY=0`` (A/B runs): a model with a scale_x_y head decodes (YH_OP_DECODE_SXY) and then filters, instead of the
+        fused candidate pass."""
+        if os.environ.get('YOLO_HIP_SCALE_XY', '1') != '0':
+            return False
+        if plan is not None:
+            return any(isinstance(d, hiplib.DecodeSxyDesc) for d in plan['decode_descs'])
+        return any(getattr(m, 'scale_x_y', 1.0) != 1.0 for m in self.model.module_list if m.__class__.__name__ == 'YOLOLayer')
 
     # ------------------------------------------------------------------------ test-time augmentation
     def _tta_inputs(self, x):
@@ -1000,7 +1012,8 @@ class DarknetEngine:
         groups = tta_groups(tta_views(x.shape[2], x.shape[3]))
         N = x.shape[0]
         graph = x.is_cuda and hasattr(self.lib, 'yh_plan_graph_launch') and any(0 < len(m) * N <= self.graph_max_batch for m in groups)
-        if graph or self.return_features or os.environ.get('YOLO_HIP_FUSED_DETECT', '1') == '0' or len(groups) > self.max_plans:
+        if graph or self.return_features or os.environ.get('YOLO_HIP_FUSED_DETECT', '1') == '0' or len(groups) > self.max_plans \
+                or self._scaled_two_pass(None):
             return hnms.non_max_suppression(self.forward_augmented(x), conf_thres, iou_thres, multi_label, classes, agnostic)
         x, views, inputs = self._tta_inputs(x)
         W = x.shape[3]
@@ -1023,11 +1036,12 @@ class DarknetEngine:
                 off = sum(rows_of[i] for i in range(k))
                 scale, flip_w = self._tta_transform(views[k], W)
                 heads = []
-                for d in plan['decode_descs']:
-                    e = DecodeDesc.from_buffer_copy(d)
+                for desc in plan['decode_descs']:
+                    copy = type(desc).from_buffer_copy(desc)         # a scaled head stays a yh_decode_sxy_desc
+                    d, e = hiplib.decode_base(desc), hiplib.decode_base(copy)
                     e.p = d.p + j * N * d.ny * d.nx * d.ldp * 4      # this view's images inside the stacked batch
                     e.n, e.rows_total, e.row_off = N, total, off + d.row_off
-                    heads.append((e, scale, flip_w))
+                    heads.append((copy, scale, flip_w))
                 entries[k] = heads
         return hnms.non_max_suppression_heads([h for heads in entries for h in heads], N, total, no - 5, x.device, conf_thres, iou_thres,
                                               multi_label, classes, agnostic)

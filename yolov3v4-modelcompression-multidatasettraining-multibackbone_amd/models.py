@@ -127,7 +127,7 @@ def _graph_stride(scales, mdef, src):
 
 
 def create_modules(module_defs, img_size, cfg, quantized, quantizer_output, layer_idx, reorder, TM, TN, a_bit=8,
-                   w_bit=8, steps=0, is_gray_scale=False, maxabsscaler=False, shortcut_way=-1):
+                   w_bit=8, steps=0, is_gray_scale=False, maxabsscaler=False, shortcut_way=-1, scale_x_y=False):
     """Walk the parsed cfg blocks and emit one module per block.
 
     Returns ``(nn.ModuleList, routs)`` where ``routs[i]`` says whether block i's output is read again
@@ -227,7 +227,8 @@ def create_modules(module_defs, img_size, cfg, quantized, quantizer_output, laye
             modules = YOLOLayer(anchors=mdef['anchors'][mdef['mask']], nc=mdef['classes'], img_size=img_size,
                                 yolo_index=yolo_index, layers=layers,
                                 stride=_head_stride(cfg, yolo_index, scale_hist[-1]),
-                                quantizer_output=quantizer_output)
+                                quantizer_output=quantizer_output,
+                                scale_x_y=head_scale_xy(mdef, i + 1) if scale_x_y else 1.0)
             _smart_bias_init(module_list, modules, layers, yolo_index, 'from' in mdef)
 
         else:
@@ -241,6 +242,20 @@ def create_modules(module_defs, img_size, cfg, quantized, quantizer_output, laye
     for r in routed:
         routs[r] = True
     return module_list, routs
+
+
+def head_scale_xy(mdef, block):
+    """darknet's ``scale_x_y`` of a ``[yolo]`` block ("grid sensitivity": the centre is ``sigmoid(t) * s - (s - 1) / 2``, so it can
+    reach and cross its cell's border); 1.0 where the key is missing.  Accepted: finite, ``1 <= s <= 2`` (darknet's own cfgs use
+    1.05 .. 2.0); anything else raises a ``ValueError`` that names the block (``block``: its index in the cfg, ``[net]`` being 0)."""
+    raw = mdef.get('scale_x_y', 1.0)
+    try:
+        s = float(raw)
+    except (TypeError, ValueError):
+        s = float('nan')
+    if not (math.isfinite(s) and 1.0 <= s <= 2.0):
+        raise ValueError('cfg block %d [%s]: scale_x_y = %r is not a finite value in [1, 2]' % (block, mdef.get('type'), raw))
+    return s
 
 
 def _head_stride(cfg, yolo_index, graph_scale):
@@ -280,11 +295,13 @@ class YOLOLayer(nn.Module):
 
     Input ``p`` is (bs, na*no, ny, nx).  Train: returns the raw (bs, na, ny, nx, no) view.  Eval:
     ``xy = (sigmoid(t_xy) + cell) * stride``, ``wh = exp(t_wh) * anchor``, ``sigmoid`` on obj/cls;
-    returns ``(io.view(bs, -1, no), raw)``.
+    returns ``(io.view(bs, -1, no), raw)``.  ``scale_x_y`` (darknet's key of the section, taken only when the model asks for it:
+    ``Darknet(scale_x_y=True)``) makes the centre ``sigmoid(t_xy) * s - 0.5 * (s - 1) + cell``; 1.0 is the statement above, bit for bit.
     """
 
-    def __init__(self, anchors, nc, img_size, yolo_index, layers, stride, quantizer_output=False):
+    def __init__(self, anchors, nc, img_size, yolo_index, layers, stride, quantizer_output=False, scale_x_y=1.0):
         super().__init__()
+        self.scale_x_y = float(scale_x_y)
         self.anchors = torch.Tensor(anchors)
         self.index = yolo_index
         self.layers = layers
@@ -316,7 +333,11 @@ class YOLOLayer(nn.Module):
         if self.training:
             return p
         io = p.clone()
-        io[..., :2] = torch.sigmoid(io[..., :2]) + self.grid
+        if self.scale_x_y == 1.0:
+            io[..., :2] = torch.sigmoid(io[..., :2]) + self.grid
+        else:
+            s = self.scale_x_y
+            io[..., :2] = torch.sigmoid(io[..., :2]) * s - 0.5 * (s - 1) + self.grid
         io[..., 2:4] = torch.exp(io[..., 2:4]) * self.anchor_wh
         io[..., :4] *= self.stride
         torch.sigmoid_(io[..., 4:])
@@ -381,8 +402,10 @@ class Darknet(nn.Module):
 
     def __init__(self, cfg, img_size=(416, 416), verbose=False, quantized=-1, a_bit=8, w_bit=8,
                  quantizer_output=False, layer_idx=-1, reorder=False, TM=32, TN=32, steps=0, is_gray_scale=False,
-                 maxabsscaler=False, shortcut_way=-1, **ignored):
+                 maxabsscaler=False, shortcut_way=-1, scale_x_y=False, **ignored):
         # **ignored: detect.py:26 / convert_FPGA.py:18 pass FPGA=..., which the reference rejects
+        # scale_x_y: honour the [yolo] sections' scale_x_y (YOLOv4's grid sensitivity) in decode and loss.  The reference ignores the
+        # key, and so does False: every head is 1.0 then.  True with a cfg that has no such key is not an error (all heads 1.0)
         super().__init__()
         if isinstance(cfg, str):
             self.module_defs = parse_model_cfg(cfg)
@@ -400,11 +423,16 @@ class Darknet(nn.Module):
         self.TN = TN
         self.is_gray_scale = is_gray_scale
 
+        self.scale_x_y = bool(scale_x_y)
+        if self.scale_x_y:      # a value outside [1, 2] raises here, before any module is built
+            for i, mdef in enumerate(self.module_defs):
+                if mdef.get('type') == 'yolo':
+                    head_scale_xy(mdef, i)
         self.hyperparams = copy.deepcopy(self.module_defs[0])
         self.module_list, self.routs = create_modules(
             self.module_defs, img_size, cfg, quantized=quantized, quantizer_output=quantizer_output,
             reorder=reorder, TM=TM, TN=TN, layer_idx=layer_idx, a_bit=a_bit, w_bit=w_bit, steps=steps,
-            is_gray_scale=is_gray_scale, maxabsscaler=maxabsscaler, shortcut_way=shortcut_way)
+            is_gray_scale=is_gray_scale, maxabsscaler=maxabsscaler, shortcut_way=shortcut_way, scale_x_y=self.scale_x_y)
         self.yolo_layers = get_yolo_layers(self)
 
         self.version = np.array([0, 2, 5], dtype=np.int32)  # darknet file header: major, minor, revision

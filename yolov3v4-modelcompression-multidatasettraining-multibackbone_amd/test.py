@@ -88,7 +88,7 @@ def host_stats(output, targets, height, width, iouv):
 
 def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, iou_thres=0.6, save_json=False, augment=False,
          model=None, dataloader=None, multi_label=True, quantized=-1, a_bit=8, w_bit=8, rank=-1, plot=True, is_gray_scale=False,
-         maxabsscaler=False, shortcut_way=-1, coco_metrics=False):
+         maxabsscaler=False, shortcut_way=-1, coco_metrics=False, scale_x_y=False):
     global coco_result
     if model is None:
         device = torch_utils.select_device(opt.device if opt is not None else '', batch_size=batch_size)
@@ -96,7 +96,7 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
         for f in glob.glob('test_batch*.jpg'):
             os.remove(f)
         model = Darknet(cfg, imgsz, quantized=quantized, a_bit=a_bit, w_bit=w_bit, is_gray_scale=is_gray_scale,
-                        maxabsscaler=maxabsscaler, shortcut_way=shortcut_way)
+                        maxabsscaler=maxabsscaler, shortcut_way=shortcut_way, scale_x_y=scale_x_y)
         if weights:
             attempt_download(weights)
             if weights.endswith('.pt'):
@@ -251,7 +251,7 @@ def test(cfg, data, weights=None, batch_size=16, imgsz=416, conf_thres=0.001, io
     return (mp, mr, map50, mf1, *(loss.cpu() / max(len(dataloader), 1)).tolist()), maps
 
 
-if __name__ == '__main__':
+def make_parser():
     parser = argparse.ArgumentParser(prog='test.py')
     parser.add_argument('--cfg', type=str, default='cfg/yolov3/yolov3.cfg', help='*.cfg path')
     parser.add_argument('--data', type=str, default='data/coco2014.data', help='*.data path')
@@ -266,6 +266,10 @@ if __name__ == '__main__':
     parser.add_argument('--task', default='test', help="'test', 'study', 'benchmark'")
     parser.add_argument('--device', default='', help='device id (i.e. 0 or 0,1) or cpu')
     parser.add_argument('--augment', action='store_true', help='augmented inference')
+    parser.add_argument('--scale-x-y', action='store_true',
+                        help="honour the scale_x_y key of the cfg's [yolo] sections (YOLOv4's grid sensitivity: box centre = sigmoid * s - "
+                             '(s - 1) / 2, 1.2 / 1.1 / 1.05 on the YOLOv4 heads) in decode and NMS filter (and in the validation loss).  Off'
+                             ' by default: the reference ignores the key')
     parser.add_argument('--host-letterbox', action='store_true', help='resize / letterbox the evaluation images on the host (default on a GPU: on the device)')
     parser.add_argument('--image-arith', choices=['pillow', 'cv2'], default=None,
                         help="uint8 arithmetic of the device loader: 'pillow' = the host loader's, 'cv2' = the reference's OpenCV calls restated")
@@ -275,7 +279,11 @@ if __name__ == '__main__':
     parser.add_argument('--w-bit', type=int, default=8, help='w-bit')
     parser.add_argument('--gray-scale', action='store_true', help='gray scale training')
     parser.add_argument('--maxabsscaler', '-mas', action='store_true', help='standardise input to (-1, 1)')
-    opt = parser.parse_args()
+    return parser
+
+
+if __name__ == '__main__':
+    opt = make_parser().parse_args()
     opt.save_json = opt.save_json or any(x in opt.data for x in ('coco.data', 'coco2014.data', 'coco2017.data'))
     for key in ('cfg', 'data'):
         found = glob.glob('./**/' + getattr(opt, key), recursive=True)
@@ -285,11 +293,12 @@ if __name__ == '__main__':
     if opt.task == 'test':
         test(opt.cfg, opt.data, opt.weights, opt.batch_size, opt.img_size, opt.conf_thres, opt.iou_thres, opt.save_json, opt.augment,
              quantized=opt.quantized, a_bit=opt.a_bit, w_bit=opt.w_bit, is_gray_scale=opt.gray_scale, maxabsscaler=opt.maxabsscaler,
-             shortcut_way=opt.shortcut_way, coco_metrics=opt.coco_metrics)
+             shortcut_way=opt.shortcut_way, coco_metrics=opt.coco_metrics, scale_x_y=opt.scale_x_y)
     elif opt.task == 'benchmark':   # mAP / speed over a grid of sizes and NMS thresholds
         rows = []
         for size in (320, 416, 512, 608):
             for iou in (0.6, 0.7):
-                res, _ = test(opt.cfg, opt.data, opt.weights, opt.batch_size, size, opt.conf_thres, iou, opt.save_json)
+                res, _ = test(opt.cfg, opt.data, opt.weights, opt.batch_size, size, opt.conf_thres, iou, opt.save_json,
+                              scale_x_y=opt.scale_x_y)
                 rows.append(res)
         np.savetxt('benchmark.txt', rows, fmt='%10.4g')

@@ -190,7 +190,8 @@ def train(opt, hyp):
 
     steps = math.ceil(len(open(train_path).readlines()) / batch_size) * epochs if os.path.isfile(train_path) else 0
     model = Darknet(cfg, quantized=opt.quantized, a_bit=opt.a_bit, w_bit=opt.w_bit, steps=steps, is_gray_scale=opt.gray_scale,
-                    maxabsscaler=opt.maxabsscaler, shortcut_way=opt.shortcut_way).to(device)
+                    maxabsscaler=opt.maxabsscaler, shortcut_way=opt.shortcut_way,
+                    scale_x_y=getattr(opt, 'scale_x_y', False)).to(device)      # the EMA copy and test.test below use these modules
     t_model = load_teacher(opt.t_cfg, opt.t_weights, device) if opt.t_cfg else None
     configure_distillation(model, t_model, opt.KDstr, device)
 
@@ -398,7 +399,7 @@ def train(opt, hyp):
                                              model=ema.ema if ema is not None else core, save_json=False, dataloader=testloader,
                                              multi_label=ni > n_burn, quantized=opt.quantized, a_bit=opt.a_bit, w_bit=opt.w_bit,
                                              rank=rank, plot=False, is_gray_scale=opt.gray_scale, maxabsscaler=opt.maxabsscaler,
-                                             shortcut_way=opt.shortcut_way)
+                                             shortcut_way=opt.shortcut_way, scale_x_y=getattr(opt, 'scale_x_y', False))
         if _is_main(rank):
             with open(results_file, 'a') as f:
                 f.write(line + '%10.3g' * 7 % tuple(results) + '\n')
@@ -499,6 +500,11 @@ def make_parser():
                         help="box regression measure of compute_loss (and of its objectness target); 'cfg' takes the iou_loss key of "
                              "the cfg's [yolo] sections (the YOLOv4 cfgs say ciou; none: giou).  On a GPU the fused loss kernels carry "
                              'all three (YOLO_HIP_BOX_LOSS=0 keeps the torch statement for diou / ciou)')
+    parser.add_argument('--scale-x-y', action='store_true',
+                        help="honour the scale_x_y key of the cfg's [yolo] sections (YOLOv4's grid sensitivity: box centre = sigmoid * s - "
+                             '(s - 1) / 2, 1.2 / 1.1 / 1.05 on the YOLOv4 heads) in decode, NMS filter and loss.  Off by default: the '
+                             'reference ignores the key.  On a GPU the engines and the fused loss kernels carry it (YOLO_HIP_SCALE_XY=0 '
+                             'keeps the torch statements)')
     parser.add_argument('--label-smoothing', type=_label_smoothing, default=None,
                         help="label smoothing eps of the class targets (1 - eps / 2, eps / 2), 0 <= eps < 1; default: the hyp dict's "
                              'label_smoothing or 0')

@@ -248,13 +248,17 @@ def compute_loss(p, targets, model, fused=None):
     ``model.box_loss`` ('giou' when the model has none; 'diou' / 'ciou' are darknet's ``iou_loss`` of the YOLOv4 cfgs) selects the
     ``bbox_iou`` measure of the box term and of the objectness target; ``hyp['label_smoothing']`` (0 when absent) is ``smooth_BCE``'s
     eps.  CIoU of a prediction that equals its label exactly is nan here, the reference's arithmetic (alpha = 0 / 0); the fused
-    kernels take the limit there (include/yolo_hip.h)."""
+    kernels take the limit there (include/yolo_hip.h).
+
+    A head with darknet's ``scale_x_y`` s != 1 (``Darknet(scale_x_y=True)``, read from the model's yolo modules in head order) has
+    ``pxy = sigmoid(ps[:, 0:2]) * s - 0.5 * (s - 1)``; everything downstream, ``build_targets`` included, is unchanged.  The fused
+    kernels take it too (``yh_yolo_loss_head_*``) unless ``YOLO_HIP_SCALE_XY=0`` keeps these torch statements."""
     kind = getattr(model, 'box_loss', 'giou')
     if kind not in BOX_LOSSES:
         raise ValueError('unknown box loss %r: expected one of %s' % (kind, ', '.join(BOX_LOSSES)))
     if fused is not False and (p[0].is_cuda or _fused_loss_override()):
         from engine import loss as hip_loss
-        if hip_loss.usable(p, model):
+        if hip_loss.usable(p, model, scaled=any(v != 1.0 for v in hip_loss.head_scales(model, _yolo_modules))):
             return hip_loss.compute_loss(p, targets, model, _yolo_modules, smooth_BCE)
     dev = p[0].device
     z = lambda: torch.zeros(1, device=dev)
@@ -266,6 +270,7 @@ def compute_loss(p, targets, model, fused=None):
     cp, cn = smooth_BCE(eps=h.get('label_smoothing', 0.0))
     if h['fl_gamma'] > 0:
         bce_cls, bce_obj = FocalLoss(bce_cls, h['fl_gamma']), FocalLoss(bce_obj, h['fl_gamma'])
+    sxy = [float(getattr(layer, 'scale_x_y', 1.0)) for layer in _yolo_modules(model)]
     for i, pi in enumerate(p):
         b, a, gj, gi = indices[i]
         tobj = torch.zeros_like(pi[..., 0])
@@ -273,6 +278,8 @@ def compute_loss(p, targets, model, fused=None):
         if nb:
             ps = pi[b, a, gj, gi]
             pxy = torch.sigmoid(ps[:, 0:2])
+            if sxy[i] != 1.0:
+                pxy = pxy * sxy[i] - 0.5 * (sxy[i] - 1)
             pwh = torch.exp(ps[:, 2:4]).clamp(max=1E3) * anchor_vec[i]
             giou = bbox_iou(torch.cat((pxy, pwh), 1).t(), tbox[i], x1y1x2y2=False, **{BOX_LOSSES[kind]: True})
             lbox = lbox + (1.0 - giou).mean()

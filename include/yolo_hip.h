@@ -1134,21 +1134,18 @@ int yh_plan_num_ops(const yh_plan* p);
 int yh_plan_run(yh_plan* p, void* stream);
 /* run ops [first, last) only (profiling / per-layer tests) */
 int yh_plan_run_range(yh_plan* p, int first, int last, void* stream);
-/* Two lanes.  Ops are replayed in index order on the caller's stream (lane 0) unless marked lane 1, which runs on a stream owned
- * by the plan; across lanes the only ordering is what yh_plan_add_dep states (op waits for the completion of dep, dep < op), and
- * every yh_plan_run / yh_plan_run_range call joins the side lane into the caller's stream before it returns.  The training
- * backward puts the weight gradients on lane 1: they only feed the optimizer, so the HBM-bound BatchNorm backward passes of the
- * next layer run underneath them (engine/train.py).                                                                        */
+/* Scheduling hints, accepted and ignored.  Every op of a run is replayed in index order on the caller's stream.  That is a valid
+ * execution of anything these entries can state (a lane 0 / 1 per op; op waits for the completion of dep, dep < op; reduce launches
+ * that join before the run returns), so a caller of ABI 2 that states it keeps working: the arguments are checked as before
+ * (YH_EINVAL for a NULL plan; YH_ERANGE for an op index past the end, a lane other than 0 / 1, dep >= op) and nothing is stored.
+ * The mechanisms behind them (a side stream for the weight gradients, a reduce stream) measured no gain: DESIGN.md 3.3 (d), (e).  */
 int yh_plan_set_lane(yh_plan* p, int op_index, int lane);
 int yh_plan_add_dep(yh_plan* p, int op_index, int dep_index);
+int yh_plan_set_async_reduce(yh_plan* p, int enable);
 /* Per-op HIP-event timing on the launch stream: when enabled every replay brackets each op with a pair of
  * events; after the caller has synchronised the stream, yh_plan_get_timings writes the last replay's
  * per-op durations in milliseconds to the HOST array ms_out[n], n == yh_plan_num_ops.                    */
 int yh_plan_set_timing(yh_plan* p, int enable);
-/* round 6: the reduce launches of the plan's weight gradients (yh_conv2d_wgrad: partial tiles -> dW) run on a stream of their own, in the
- * shadow of the following ops; every yh_plan_run / _run_range joins before it returns.  Only for plans whose weight-gradient ops have a
- * workspace no other op uses.  Off under yh_plan_set_timing (per-op times stay additive). */
-int yh_plan_set_async_reduce(yh_plan* p, int enable);
 int yh_plan_get_timings(yh_plan* p, float* ms_out, int n);
 /* hipGraph replay for launch-bound (small batch) forwards: capture records one replay with the currently bound
  * slot pointers on a non-null stream; launch replays it with a single graph launch; reset drops the graph (needed

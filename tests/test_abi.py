@@ -67,6 +67,19 @@ def test_plan_api_runs_without_gpu():
     assert lib.yh_plan_add_fixup(h, 0, hiplib.CopyDesc.x.offset, 0, 0) == 0
     assert lib.yh_plan_add_fixup(h, 5, 0, 0, 0) == -5  # YH_ERANGE
     assert lib.yh_plan_run(h, None) == -1  # unbound slot -> YH_EINVAL, nothing launched
+    # the scheduling hints of ABI 2 (accepted and ignored): on a two-op plan they still answer what they always answered
+    assert lib.yh_plan_add(h, hiplib.OP_COPY, C.byref(d), C.sizeof(d)) == 1 and lib.yh_plan_num_ops(h) == 2
+    EINVAL, ERANGE = -1, -5
+    assert [lib.yh_plan_set_lane(h, op, lane) for op in (0, 1) for lane in (0, 1)] == [0] * 4
+    assert lib.yh_plan_add_dep(h, 1, 0) == 0 and lib.yh_plan_set_async_reduce(h, 1) == 0 and lib.yh_plan_set_async_reduce(h, 0) == 0
+    assert lib.yh_plan_set_lane(h, 2, 1) == ERANGE and lib.yh_plan_set_lane(h, -1, 0) == ERANGE     # op index past the end
+    assert lib.yh_plan_set_lane(h, 0, 2) == ERANGE and lib.yh_plan_set_lane(h, 0, -1) == ERANGE     # no such lane
+    assert lib.yh_plan_add_dep(h, 2, 0) == ERANGE                                                   # op index past the end
+    assert lib.yh_plan_add_dep(h, 1, 1) == ERANGE and lib.yh_plan_add_dep(h, 0, 0) == ERANGE        # dep == op
+    assert lib.yh_plan_add_dep(h, 1, 2) == ERANGE and lib.yh_plan_add_dep(h, 1, -1) == ERANGE       # dep past the end
+    assert lib.yh_plan_set_lane(None, 0, 1) == EINVAL and lib.yh_plan_add_dep(None, 1, 0) == EINVAL
+    assert lib.yh_plan_set_async_reduce(None, 1) == EINVAL
+    assert lib.yh_plan_num_ops(h) == 2 and lib.yh_plan_run(h, None) == -1                           # and they changed nothing
     lib.yh_plan_destroy(h)
 
 

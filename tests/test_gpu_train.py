@@ -1320,6 +1320,54 @@ def test_training_step_is_run_to_run_deterministic(libs, net, precision):
           % (net.split('/')[0], precision, len(first[0]), len(first[2])))
 
 
+@pytest.mark.parametrize('precision', ['fp16', 'fp32'])
+@pytest.mark.parametrize('size', [4, 52])
+def test_scheduling_hints_do_not_change_a_step(libs, mini, size, precision):
+    """yh_plan_set_lane / yh_plan_add_dep / yh_plan_set_async_reduce are accepted and ignored (include/yolo_hip.h).  The mini cfg at
+    4 x 4, batch 3: the smallest square input at which a weight gradient asks for a workspace (yh_conv2d_wgrad_workspace > 0 - the
+    two-stage reduce, whose launches the reduce stream used to take, is on the path).  Queried on the CPU through the library: all 14
+    weight gradients ask for 8192 or 16384 floats at every size from 4 x 4, the smallest the graph accepts (grids 2 x 2 and 1 x 1), so
+    the rule gives 4; 52 (grids 26 and 13, launches of several workgroups with tails) is run as well.  The same step with fixed
+    head-gradient weights twice: raw heads and parameter gradients must be the same bits, or nothing below means anything.  Then
+    every weight gradient of the backward plan is marked lane 1 with a dependency on the op before it, async reduce is switched on,
+    and the step runs again: still the same bits."""
+    if DRY:
+        pytest.skip('the hint entries are the library\'s: the host emulation has none')
+    batch = 3
+    m = th.build(mini, size).to(GPU)
+    x = synth.image_batch(batch, size, seed=0).to(GPU)
+    state = {}
+
+    def step():
+        for p in m.parameters():
+            p.grad = None
+        os.environ['YOLO_HIP_TRAIN_PRECISION'] = precision
+        try:
+            raws, _ = m._forward_hip_train(x)
+        finally:
+            del os.environ['YOLO_HIP_TRAIN_PRECISION']
+        ws = state.setdefault('ws', th.loss_weights(raws))
+        th.toy_loss(raws, ws).backward()
+        _sync()
+        return [r.detach().clone() for r in raws], {k: p.grad.detach().clone() for k, p in m.named_parameters()}
+
+    def same(a, b):
+        return all(torch.equal(u, v) for u, v in zip(a[0], b[0])) and all(torch.equal(a[1][k], b[1][k]) for k in a[1])
+    first = step()
+    eng = m.__dict__['_hip_train_engine']
+    lib, plan = eng.lib, eng._current
+    wgrads = [i for i, (_, d) in enumerate(plan['bwd_ops']) if isinstance(d, hiplib.WgradDesc)]
+    assert len(wgrads) >= 10 and any(d.ws_floats > 0 for _, d in plan['bwd_ops'] if isinstance(d, hiplib.WgradDesc))
+    assert len(first[1]) == len(list(m.parameters())) and all(bool(g.abs().sum() > 0) for g in first[1].values())
+    assert same(first, step()), 'graph not reproducible'
+    for i in wgrads:
+        assert lib.yh_plan_set_lane(plan['bwd'], i, 1) == 0 and lib.yh_plan_add_dep(plan['bwd'], i, i - 1) == 0
+    assert lib.yh_plan_set_async_reduce(plan['bwd'], 1) == 0
+    hinted = step()
+    assert m.__dict__['_hip_train_engine'] is eng and eng._current is plan
+    assert same(first, hinted), 'the step changed under the scheduling hints'
+
+
 def test_step_with_backward_sums_in_the_data_gradient_equals_the_plain_step(libs, monkeypatch):
     """Round 6 (yh_conv_desc.bwd_z) inside a whole step on the GPU: YOLOv3 at 608 x 608, batch 3 (304^2 x 3 >= 262 144 pixels: the first
     residual stage's 1x1 data gradient runs on the persistent kernel and carries the backward sums of the block it completes), fp16, in

@@ -90,6 +90,57 @@ def engine_step(model, x, ws, precision, lib=None, device='cpu'):
     return [r.detach().float().cpu() for r in raws], grads, m
 
 
+PLAN_CASES = [(cfg, precision, False) for cfg in ('yolov3/yolov3.cfg', 'yolov4/yolov4.cfg', 'yolov3-mobilenet/yolov3-mobilenet-coco.cfg')
+              for precision in ('fp16', 'fp32')] + [('yolov3/yolov3.cfg', 'fp16', True)]
+
+
+def plan_fingerprint(cfg, precision, attention=False, size=64, batch=2):
+    """Build (never run) the training plan of ``cfg`` (a path below cfg/) on the host emulation and digest what the builder handed
+    the plan API.  Per op: log name, kind, every non-pointer field (arrays as bytes), per pointer field null / fixup / other, and
+    the sorted fixups (field offset, slot, byte offset) - the byte offsets pin the arena layout of every piece.  The emulation's
+    weight-gradient workspace queries answer a non-zero constant, so the weight gradients' workspace fixups are in the digest."""
+    import ctypes as C
+    import hashlib
+    import fakelib
+    from engine.padded import make_train_engine
+
+    class Lib(fakelib.FakeLib):
+        def yh_conv2d_wgrad_workspace(self, dref):
+            return 4096
+
+        def yh_dw_wgrad_workspace(self, dref):
+            return 4096
+
+    lib = Lib()
+    torch.manual_seed(0)
+    model = Darknet(os.path.join(conftest.PKG, 'cfg', cfg), (size, size)).train()
+    shape = (batch, 3, size, size)
+    eng = make_train_engine(model, precision, shape, lib=lib)
+    eng = getattr(eng, 'inner', eng)
+    eng.attention = attention
+    plan = eng._cached_plan(eng._plan_key(shape))
+    out = dict(cfg=cfg, precision=precision, attention=attention, arena_need=plan['arena_need'])
+    h = hashlib.sha256()
+    for side in ('fwd', 'bwd'):
+        ops, log = lib.plans[fakelib._addr(plan[side])]['ops'], plan[side + '_ops']
+        assert len(ops) == len(log)
+        out['n_' + side] = len(ops)
+        for (kind, desc, fixups), (what, _) in zip(ops, log):
+            fixed = {off for off, _, _ in fixups}
+            h.update(('%s|%d|' % (what, kind)).encode())
+            for name, ctype in desc._fields_:
+                field = getattr(type(desc), name)
+                raw = bytes(desc)[field.offset:field.offset + field.size]
+                pointer = ctype is C.c_void_p or getattr(ctype, '_type_', None) is C.c_void_p
+                h.update(('%s=' % name).encode())
+                h.update((b'fixup' if field.offset in fixed else b'other' if any(raw) else b'null') if pointer else raw)
+                h.update(b';')
+            h.update(repr(sorted(fixups)).encode())
+            h.update(b'\n')
+    out['sha256'] = h.hexdigest()
+    return out
+
+
 def rel_l2(a, b):
     return (a - b).norm().item() / (b.norm().item() + 1e-20)
 

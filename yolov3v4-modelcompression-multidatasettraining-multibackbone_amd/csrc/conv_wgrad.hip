@@ -970,7 +970,6 @@ extern "C" int yh_conv2d_wgrad(const yh_wgrad_desc* d, void* stream) {
         a.xcd_splits = splits;
         grid = dim3((unsigned)(tiles * splits), 1);
     }
-    if (a.two_stage) reduce_guard_workspace(st);      // a previous weight gradient's reduce may still be reading the workspace
     if (a.dma) {
         if (narrow) hipLaunchKernelGGL((conv_wgrad_dma_kernel<2, 2>), grid, dim3(256), 0, st, a);
         else if (a.bm == 256) hipLaunchKernelGGL((conv_wgrad_dma_kernel<8, 2>), grid, dim3(256), 0, st, a);
@@ -987,8 +986,6 @@ extern "C" int yh_conv2d_wgrad(const yh_wgrad_desc* d, void* stream) {
         if (groups > 32) groups = 32;                       // groups are the expensive part (4x more groups measured 30 % slower)
         const int per_group = (splits + groups - 1) / groups;
         groups = (splits + per_group - 1) / per_group;
-        const hipStream_t ms = st;
-        st = reduce_begin(ms);
         auto reduce = [&](int ngroups, int nsplits, int per, int sstep, int native) {
             if (narrow) hipLaunchKernelGGL((wgrad_reduce_kernel<2, 2>), dim3(tiles * 8, ngroups), dim3(256), 0, st, a, nsplits, per, sstep, native);
             else if (a.bm == 256) hipLaunchKernelGGL((wgrad_reduce_kernel<8, 2>), dim3(tiles * 32, ngroups), dim3(256), 0, st, a, nsplits, per, sstep, native);
@@ -1000,7 +997,6 @@ extern "C" int yh_conv2d_wgrad(const yh_wgrad_desc* d, void* stream) {
         } else {
             reduce(groups, splits, per_group, 1, 0);
         }
-        reduce_end(ms, st);
     }
     return check_launch();
 }

@@ -414,10 +414,7 @@ int launch_wgrad_roll(const yh_wgrad_desc* d, hipStream_t st) {
     if (!d->ws || d->ws_floats < (int64_t)splits * tiles * 128 * 576) return YH_EUNSUPPORTED;
     const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv_wgrad_roll_kernel), lds);
     if (e != hipSuccess) return (int)e;
-    reduce_guard_workspace(st);       // a previous weight gradient's reduce may still be reading the workspace (common.h AsyncReduce)
     hipLaunchKernelGGL(conv_wgrad_roll_kernel, dim3((unsigned)(tiles * splits)), dim3(768), lds, st, a);
-    const hipStream_t ms = st;
-    st = reduce_begin(ms);                // the reduce launches below: on the plan's reduce stream when it has one
     int groups = (256 + tiles * 32 - 1) / (tiles * 32);       // >= one workgroup per CU where the splits allow it
     if (groups > splits / 4) groups = splits / 4;
     if (groups < 1) groups = 1;
@@ -434,7 +431,6 @@ int launch_wgrad_roll(const yh_wgrad_desc* d, hipStream_t st) {
     } else {
         reduce(groups, splits, per_group, 1, 0);
     }
-    reduce_end(ms, st);
     return check_launch();
 }
 

@@ -8,10 +8,6 @@
 
 #include "common.h"
 
-namespace yh {
-thread_local AsyncReduce* g_async_reduce = nullptr;
-}
-
 namespace {
 
 union AnyDesc {
@@ -48,9 +44,6 @@ struct Op {
     int kind;
     AnyDesc d;
     std::vector<Fixup> fixups;
-    int lane = 0;                 // 0: the caller's stream; 1: the plan's side stream (yh_plan_set_lane)
-    std::vector<int> deps;        // ops of the OTHER lane this one waits for (yh_plan_add_dep); same-lane order is the stream's
-    bool has_dependents = false;  // some op of the other lane waits for this one: record its event
 };
 
 size_t desc_size(int kind) {
@@ -131,14 +124,6 @@ struct yh_plan {
     // optional hipGraph of one replay (launch-bound small batches): valid for the slot pointers bound at capture
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
-    // second lane: ops the planner marked as independent of the main chain (the weight gradients of the training backward) run
-    // on this stream, ordered against the main lane by explicit dependencies only; every range joins before it returns
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> done;   // done[i]: recorded after op i when has_dependents (created lazily, timing disabled)
-    hipEvent_t join = nullptr;
-    // weight-gradient reduce launches on their own stream (yh_plan_set_async_reduce; common.h AsyncReduce)
-    bool async_reduce = false;
-    yh::AsyncReduce ar;
     void drop_graph() {
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -147,12 +132,6 @@ struct yh_plan {
     }
     ~yh_plan() {
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
-        for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e);
-        if (join) (void)hipEventDestroy(join);
-        if (side) (void)hipStreamDestroy(side);
-        if (ar.main_done) (void)hipEventDestroy(ar.main_done);
-        if (ar.red_done) (void)hipEventDestroy(ar.red_done);
-        if (ar.side) (void)hipStreamDestroy(ar.side);
         drop_graph();
     }
 };
@@ -219,30 +198,29 @@ extern "C" int yh_plan_bind_slot(yh_plan* p, int slot, void* ptr) {
 
 extern "C" int yh_plan_num_ops(const yh_plan* p) { return p ? (int)p->ops.size() : YH_EINVAL; }
 
+// Scheduling hints of ABI 2, accepted and ignored: every op runs in index order on the caller's stream, which satisfies any dependency
+// that can be declared (dep < op).  The argument checks and their return codes are the ones the entries always had.
 extern "C" int yh_plan_set_lane(yh_plan* p, int op_index, int lane) {
     if (!p) return YH_EINVAL;
     if (op_index < 0 || op_index >= (int)p->ops.size() || lane < 0 || lane > 1) return YH_ERANGE;
-    p->ops[op_index].lane = lane;
     return YH_OK;
 }
 
 extern "C" int yh_plan_add_dep(yh_plan* p, int op_index, int dep_index) {
     if (!p) return YH_EINVAL;
     if (op_index < 0 || op_index >= (int)p->ops.size() || dep_index < 0 || dep_index >= op_index) return YH_ERANGE;
-    try {
-        p->ops[op_index].deps.push_back(dep_index);
-    } catch (...) {
-        return YH_ENOMEM;
-    }
-    p->ops[dep_index].has_dependents = true;
     return YH_OK;
+}
+
+extern "C" int yh_plan_set_async_reduce(yh_plan* p, int enable) {
+    (void)enable;
+    return p ? YH_OK : YH_EINVAL;
 }
 
 extern "C" int yh_plan_run_range(yh_plan* p, int first, int last, void* stream) {
     if (!p) return YH_EINVAL;
     if (first < 0 || last > (int)p->ops.size() || first > last) return YH_ERANGE;
-    hipStream_t main_s = (hipStream_t)stream;
-    bool side_used = false;
+    hipStream_t s = (hipStream_t)stream;
     for (int i = first; i < last; ++i) {
         const Op& op = p->ops[i];
         AnyDesc d = op.d;
@@ -252,73 +230,11 @@ extern "C" int yh_plan_run_range(yh_plan* p, int first, int last, void* stream) 
             void* v = base == YH_SLOT_NULL ? nullptr : (void*)((char*)base + f.byte_offset);   // bound to "nothing": optional outputs
             memcpy((char*)&d + f.field_offset, &v, sizeof(void*));
         }
-        hipStream_t s = main_s;
-        if (op.lane == 1) {
-            if (!p->side) {
-                const hipError_t e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-                if (e != hipSuccess) return (int)e;
-            }
-            s = p->side;
-            side_used = true;
-        }
-        for (int dep : op.deps) {
-            // dependencies reaching into an earlier range are already satisfied: every range joins its lanes before returning
-            if (dep < first || p->ops[dep].lane == op.lane) continue;
-            const hipError_t e = hipStreamWaitEvent(s, p->done[dep], 0);
-            if (e != hipSuccess) return (int)e;
-        }
         if (p->timing) (void)hipEventRecord(p->events[2 * i], s);
-        // (per-op timing keeps the reduce launches inside the op's bracket: the numbers of the bench line stay additive)
-        const bool ar_on = p->async_reduce && !p->timing && op.kind == YH_OP_WGRAD && op.lane == 0;
-        if (ar_on) yh::g_async_reduce = &p->ar;
         const int rc = launch(op.kind, d, s);
-        yh::g_async_reduce = nullptr;
         if (p->timing) (void)hipEventRecord(p->events[2 * i + 1], s);
         if (rc != YH_OK) return rc;
-        if (op.has_dependents) {
-            if (p->done.size() < p->ops.size()) {
-                try {
-                    p->done.resize(p->ops.size(), nullptr);
-                } catch (...) {
-                    return YH_ENOMEM;
-                }
-            }
-            if (!p->done[i]) {
-                const hipError_t e = hipEventCreateWithFlags(&p->done[i], hipEventDisableTiming);
-                if (e != hipSuccess) return (int)e;
-            }
-            const hipError_t e = hipEventRecord(p->done[i], s);
-            if (e != hipSuccess) return (int)e;
-        }
     }
-    if (p->ar.pending) {      // join: dW is complete for whatever follows on the caller's stream
-        const hipError_t e = hipStreamWaitEvent(main_s, p->ar.red_done, 0);
-        if (e != hipSuccess) return (int)e;
-        p->ar.pending = false;
-    }
-    if (side_used) {   // join: whatever follows on the caller's stream sees the side lane's results
-        if (!p->join) {
-            const hipError_t e = hipEventCreateWithFlags(&p->join, hipEventDisableTiming);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipError_t e = hipEventRecord(p->join, p->side);
-        if (e == hipSuccess) e = hipStreamWaitEvent(main_s, p->join, 0);
-        if (e != hipSuccess) return (int)e;
-    }
-    return YH_OK;
-}
-
-// Weight-gradient reduce launches of this plan on their own stream.  The CALLER guarantees that the plan's weight-gradient ops do not
-// share their workspace with any other op (engine/train.py gives them SLOT_WS2).
-extern "C" int yh_plan_set_async_reduce(yh_plan* p, int enable) {
-    if (!p) return YH_EINVAL;
-    if (enable && !p->ar.side) {
-        hipError_t e = hipStreamCreateWithFlags(&p->ar.side, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ar.main_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ar.red_done, hipEventDisableTiming);
-        if (e != hipSuccess) return (int)e;
-    }
-    p->async_reduce = enable != 0;
     return YH_OK;
 }
 

@@ -52,7 +52,6 @@ _FUSED_DGRAD_MAX_CIN = int(os.environ.get('YOLO_HIP_FUSED_DGRAD_MAX', '64'))
 
 SLOT_INPUT = 0
 SLOT_WS = 1          # shared fp32 workspace of the two-stage reductions
-SLOT_WS2 = 63        # the same for the ops of the side lane (weight gradients): the two lanes run concurrently
 SLOT_HEAD0 = 2       # forward: head output tensors; backward: head gradient tensors (fp32 NHWC)
 LINEAR = hiplib.ACT_CODES['linear']
 
@@ -378,7 +377,7 @@ class TrainEngine(DarknetEngine):
         self._check_supported(values)
         self._place(values)
         lib, dev, P = self.lib, self.device, hiplib.ptr
-        plan = dict(values=values, heads=heads, N=N, storages=[], fwd_ops=[], bwd_ops=[], zero_list=[], ws_floats=0, ws2_floats=0,
+        plan = dict(values=values, heads=heads, N=N, storages=[], fwd_ops=[], bwd_ops=[], zero_list=[], ws_floats=0,
                     arena=self._arena, arena_refs=[], state=_PlanState(dev), bound=None)
         fwd = plan['fwd'] = lib.yh_plan_create()
         bwd = plan['bwd'] = lib.yh_plan_create()
@@ -403,18 +402,16 @@ class TrainEngine(DarknetEngine):
         def fixup(handle, op, desc_type, field, slot):
             hiplib.check(lib.yh_plan_add_fixup(handle, op, getattr(desc_type, field).offset, slot, 0), 'fixup')
 
-        def add_reduction(handle, log, desc, what, side=False):
-            """Reductions get the shared workspace (bound to SLOT_WS at run time) sized by the library's own query; ops of the
-            side lane have their own (SLOT_WS2)."""
+        def add_reduction(handle, log, desc, what):
+            """Reductions get the shared workspace (bound to SLOT_WS at run time) sized by the library's own query."""
             query = lib.yh_conv2d_wgrad_workspace if isinstance(desc, WgradDesc) and not isinstance(desc, StemWgradDesc) \
                 else lib.yh_dw_wgrad_workspace if isinstance(desc, DwWgradDesc) else lib.yh_bn_reduce_workspace
             need = int(query(C.byref(desc)))
             desc.ws_floats = need
-            key = 'ws2_floats' if side else 'ws_floats'
-            plan[key] = max(plan[key], need)
+            plan['ws_floats'] = max(plan['ws_floats'], need)
             op = add(handle, log, desc, what)
             if need:
-                fixup(handle, op, type(desc), 'ws', SLOT_WS2 if side else SLOT_WS)
+                fixup(handle, op, type(desc), 'ws', SLOT_WS)
             return op
 
         pieces = []
@@ -560,45 +557,8 @@ class TrainEngine(DarknetEngine):
         zero_bias = keep(max([max(_round_up(v.src.c_phys, 128), v.tpack.get('fused_m_pad', 0))
                               for v in values if v.kind == 'conv' and v.src.kind != 'input'] + [128]), torch.float32, zero=True)
         dz_elems = max(N * v.Ho * v.Wo * v.c_phys for v in values if v.kind in ('conv', 'dw'))
-        # Two lanes in the backward plan (include/yolo_hip.h yh_plan_set_lane), OFF by default: the weight gradient of a layer only
-        # feeds the optimizer, so it can run on the plan's side stream, issued after the layer's data gradient, while the main chain
-        # goes on with the HBM-bound BatchNorm backward passes of the next layer.  What the two lanes share is the dz scratch
-        # (written by a layer's BN-backward apply pass, read by its weight AND data gradient): two buffers alternate, and the writer
-        # of a buffer waits for the weight gradient that read it two layers earlier (the host emulation replays the latest schedule
-        # these dependencies allow, tests/test_train_emulated.py).  Measured on the MI355X (YOLOv3-608 b64 fp16): 63.3 vs 63.8 ms
-        # per step - the two kernels do not co-reside (a weight-gradient workgroup pair holds the whole vector register file of its
-        # CU), they time-slice: every kernel takes about twice as long while the other lane is busy.  YOLO_HIP_WGRAD_LANE=1 enables.
-        # (round 6: 2 = only the weight gradients of the <= 38 x 38 stages, 3 = only their 1x1 ones - small grids that leave CUs idle)
-        lane_mode = int(os.environ.get('YOLO_HIP_WGRAD_LANE', '0') or 0)
-        two_lanes = lane_mode > 0
-        lane_ok = lambda u: lane_mode == 1 or (lane_mode == 2 and u.Ho <= 38) or (lane_mode == 3 and u.Ho <= 38 and u.k == 1)
-        # Round 6: the reduce launches of the weight gradients (partial tiles -> dW) on the plan's reduce stream, in the shadow of the ops that
-        # follow (yh_plan_set_async_reduce).  For that the weight gradients get the second workspace to themselves: the shared one is
-        # rewritten by the very next BatchNorm reduction.  Measured (profiles/r06_async_reduce_ab.txt, three alternating rounds): 52.18 against
-        # 52.01 ms per step - the 1.3 ms of reduce launches do not hide in the following kernels' idle CUs, the events cost what little
-        # overlap there is.  OFF by default; YOLO_HIP_ASYNC_REDUCE=1 enables (same bits either way).
-        async_reduce = (not two_lanes and os.environ.get('YOLO_HIP_ASYNC_REDUCE', '0') == '1' and hasattr(lib, 'yh_plan_set_async_reduce'))
-        dz_bufs = [alloc((dz_elems,)) for _ in range(2 if two_lanes else 1)]
-        dz_state = dict(k=0, reader=[None] * len(dz_bufs))
-
-        def next_dz():
-            dz_state['k'] = (dz_state['k'] + 1) % len(dz_bufs)
-            return dz_state['k']
-
-        def dz_written_by(op, k):
-            """op is the first writer of dz buffer k for a new layer: it must not overtake the side-lane reader of the old contents."""
-            r = dz_state['reader'][k]
-            if r is not None:
-                hiplib.check(lib.yh_plan_add_dep(bwd, op, r), 'yh_plan_add_dep')
-                dz_state['reader'][k] = None
-
-        def on_side_lane(op, k):
-            """op (a weight gradient reading dz buffer k) runs on the side lane, after everything emitted so far on the main lane."""
-            if not two_lanes:
-                return
-            hiplib.check(lib.yh_plan_set_lane(bwd, op, 1), 'yh_plan_set_lane')
-            hiplib.check(lib.yh_plan_add_dep(bwd, op, op - 1), 'yh_plan_add_dep')
-            dz_state['reader'][k] = op
+        # one dz scratch, one stream: a side lane for the weight gradients and a reduce stream were measured and removed
+        dz_buf = alloc((dz_elems,))
         head_index = {id(h.src): k for k, h in enumerate(heads)}
 
         raw, n_items = self._pack_items(plan)
@@ -840,8 +800,7 @@ class TrainEngine(DarknetEngine):
                 if v.plain:
                     dzp, lddz = dyp, lddy
                 else:
-                    kz = next_dz()
-                    dzp, lddz = P(dz_bufs[kz]), v.c_phys
+                    dzp, lddz = P(dz_buf), v.c_phys
                     base, bnp = v.bn_args
                     if v.bn is not None:
                         acc = dict(bnp, sum=grads.ptr(v.g_beta), sumsq=grads.ptr(v.g_gamma))
@@ -849,8 +808,7 @@ class TrainEngine(DarknetEngine):
                         acc = dict(sum=grads.ptr(v.g_b if v.g_b is not None else self._junk(plan, grads, v.c_phys)),
                                    sumsq=grads.ptr(self._junk(plan, grads, v.c_phys)))
                     add_reduction(bwd, plan['bwd_ops'], BnBwdReduceDesc(**base, **acc, dy=dyp, lddy=lddy), 'dbn%d' % v.block)
-                    op = add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys), 'dbnx%d' % v.block)
-                    dz_written_by(op, kz)
+                    add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys), 'dbnx%d' % v.block)
                 geo = dict(n=N, h=s.H, w_in=s.W, c=v.c_phys, ho=v.H, wo=v.W, k=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, lddz=lddz,
                            dtype=self.code)
                 add_reduction(bwd, plan['bwd_ops'], DwWgradDesc(x=P(s.storage, s.c_off), dz=dzp, dw=grads.ptr(v.g_w), lddx=0, accumulate=0, **geo),
@@ -888,14 +846,11 @@ class TrainEngine(DarknetEngine):
                 continue                      # dead branch: its parameters get zero gradients
             s, pk = v.src, v.tpack
             pixels = N * v.Ho * v.Wo
-            kz = next_dz()
-            dzp, lddz = P(dz_bufs[kz]), v.c_phys
-            dz_private = True                 # dz is the scratch buffer (False: dz is dy itself, which the main lane may still change)
+            dzp, lddz = P(dz_buf), v.c_phys
             if v.fp32:                        # head: fp32 gradient from autograd -> dtype
                 op = add(bwd, plan['bwd_ops'], CastDesc(x=None, y=dzp, pixels=pixels, c=v.c_phys, ldx=v.c_phys, ldy=v.c_phys,
                                                         dtype=self.code), 'dhead%d' % v.block)
                 fixup(bwd, op, CastDesc, 'x', SLOT_HEAD0 + head_index[id(v)])
-                dz_written_by(op, kz)
                 if v.g_b is not None:         # bias gradient = sum over pixels of dz
                     add_reduction(bwd, plan['bwd_ops'],
                         BnBwdReduceDesc(z=dzp, dy=dzp, pixels=pixels, n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, ldz=v.c_phys,
@@ -923,7 +878,6 @@ class TrainEngine(DarknetEngine):
                         contribute(t, dyp, lddy, None, 'dres%d' % v.block)
                 if v.plain:                   # no BN, linear: dz is dy itself
                     dzp, lddz = dyp, lddy
-                    dz_private = False
                     if v.g_b is not None:
                         add_reduction(bwd, plan['bwd_ops'],
                             BnBwdReduceDesc(z=dyp, dy=dyp, pixels=pixels, n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, ldz=lddy,
@@ -957,9 +911,7 @@ class TrainEngine(DarknetEngine):
                         continue
                     if not getattr(v, 'dbn_done', False):     # else: the launch that completed dy took the sums (see dgrad below)
                         add_reduction(bwd, plan['bwd_ops'], BnBwdReduceDesc(**base, **acc, dy=dyp, lddy=lddy), 'dbn%d' % v.block)
-                    op = add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys),
-                             'dbnx%d' % v.block)
-                    dz_written_by(op, kz)
+                    add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys), 'dbnx%d' % v.block)
             # weight gradient
             if s.kind == 'input':
                 # the image as NHWC dtype with 8 channels (3..7 zero): the first layer then uses the MFMA wgrad kernel
@@ -967,27 +919,16 @@ class TrainEngine(DarknetEngine):
                 op = add(bwd, plan['bwd_ops'], LayoutDesc(x=None, y=P(img), n=N, c=s.C, h=s.H, w_in=s.W, c_pad=ALIGN_C, ldy=ALIGN_C,
                                                           dtype=self.code), 'image%d' % v.block)
                 fixup(bwd, op, LayoutDesc, 'x', SLOT_INPUT)
-                side = two_lanes and dz_private and lane_ok(v)
-                op = add_reduction(bwd, plan['bwd_ops'],
-                                   WgradDesc(x=P(img), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=ALIGN_C, ho=v.Ho, wo=v.Wo,
-                                             cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=ALIGN_C, lddz=lddz,
-                                             dtype=self.code, splits=0, cin_w=s.C), 'wgrad%d' % v.block, side=side)
-                if side:
-                    on_side_lane(op, kz)
+                add_reduction(bwd, plan['bwd_ops'],
+                              WgradDesc(x=P(img), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=ALIGN_C, ho=v.Ho, wo=v.Wo,
+                                        cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=ALIGN_C, lddz=lddz,
+                                        dtype=self.code, splits=0, cin_w=s.C), 'wgrad%d' % v.block)
                 continue
-            side = two_lanes and dz_private and lane_ok(v)
-
-            def emit_wgrad(v=v, s=s, dzp=dzp, lddz=lddz, kz=kz, side=side):
-                op = add_reduction(bwd, plan['bwd_ops'],
-                                   WgradDesc(x=P(s.storage, s.c_off), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=s.C, ho=v.Ho,
-                                             wo=v.Wo, cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, lddz=lddz,
-                                             dtype=self.code, splits=0), 'wgrad%d' % v.block, side=side or async_reduce)
-                if side:
-                    on_side_lane(op, kz)
-            if not side:
-                emit_wgrad()
-            # data gradient into grad(src).  With two lanes the weight gradient is issued AFTER it and waits for it: two MFMA-bound
-            # kernels gain nothing from sharing the CUs, the pairing that pays is weight gradient x the next layer's BatchNorm passes
+            add_reduction(bwd, plan['bwd_ops'],
+                          WgradDesc(x=P(s.storage, s.c_off), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=s.C, ho=v.Ho,
+                                    wo=v.Wo, cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, lddz=lddz,
+                                    dtype=self.code, splits=0), 'wgrad%d' % v.block)
+            # data gradient into grad(src)
             mode = contribution_mode(s, True)
             common = dict(bias=P(zero_bias), n=N, cin=v.c_phys, cout=s.c_phys, stride=1, ldx=lddz, ldr=s.ld if mode == 'acc' else 0,
                           ldy=s.ld, cin_k=pk['cout_k'], m_pad=pk['dm_pad'], act=LINEAR, slope=0.0, out_f32=0, dtype=self.code,
@@ -1042,8 +983,6 @@ class TrainEngine(DarknetEngine):
                     add_reduction(bwd, plan['bwd_ops'],
                                   BnBwdReduceDesc(**dict(sbase, ups=1), **sacc, dy=gptr(s), lddy=s.ld, nparts=rows), 'dbn%d' % s.block)
                     s.dbn_done = True
-            if side:
-                emit_wgrad()
         plan['head_shapes'] = [(N, h.src.H, h.src.W, h.src.c_phys) for h in heads]
         plan['segments'] = self._make_segments(plan, values, heads, bwd_pos)
         if attention:
@@ -1061,9 +1000,6 @@ class TrainEngine(DarknetEngine):
             plan['kd_table'] = keep(len(feats) * C.sizeof(hiplib.KdRow), torch.uint8, zero=True)
             plan['kd_one'] = keep(1, torch.float32, zero=True).fill_(1.0)
         plan['ws'] = alloc((max(plan['ws_floats'], 4),), fp32=True)
-        plan['ws2'] = alloc((max(plan['ws2_floats'], 4),), fp32=True)
-        if async_reduce:
-            hiplib.check(lib.yh_plan_set_async_reduce(bwd, 1), 'yh_plan_set_async_reduce')
         # place the pieces that are still in use (the residual-gradient aliasing above dropped some) and turn every pointer into
         # them into a fixup on the arena slot: the plan holds offsets, `_bind` gives it the arena's address
         need = 0
@@ -1089,7 +1025,6 @@ class TrainEngine(DarknetEngine):
         for handle in (plan['fwd'], plan['bwd']):
             lib.yh_plan_bind_slot(handle, SLOT_ARENA, base)
             lib.yh_plan_bind_slot(handle, SLOT_WS, base + plan['ws'].off)
-        lib.yh_plan_bind_slot(plan['bwd'], SLOT_WS2, base + plan['ws2'].off)
         plan['bound'] = base
         if plan.get('kd_values'):
             # the row table of the attention / inject launches holds addresses: rewritten whenever the arena moved
@@ -1114,7 +1049,7 @@ class TrainEngine(DarknetEngine):
         channels, and the first block takes the one-pass backward: then v's data gradient is computed inside that pass
         (YOLO_HIP_STEM_DGRAD=0 keeps it a launch of its own)."""
         s = v.src
-        if os.environ.get('YOLO_HIP_STEM_DGRAD', '1') == '0' or os.environ.get('YOLO_HIP_WGRAD_LANE', '0') == '1':
+        if os.environ.get('YOLO_HIP_STEM_DGRAD', '1') == '0':
             return False
         if self._building_attention:      # the first block's dy takes an injection: it has to exist as a buffer
             return False

@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
-"""What the training-plan builder (engine/train.py) hands the plan API, as recorded digests (host emulation: no GPU, no library).
+"""What the training-plan builder hands the plan API, and what it leaves in the plan dict, as recorded digests (host emulation: no
+GPU, no library).
 
     python tests/golden/make_golden_train_plan.py
 
-Writes tests/golden/train_plan_ops.json: per case of train_harness.PLAN_CASES (yolov3, yolov4 and yolov3-mobilenet at 64 x 64,
-batch 2, fp16 and fp32, plus one attention plan) the number of forward and backward ops and train_harness.plan_fingerprint's sha256
-over the op sequence.  tests/test_train_emulated.py::test_train_plan_ops_are_pinned holds the builder to it.
+Writes tests/golden/train_plan_ops.json: per case of train_harness.PLAN_CASES the number of forward and backward ops,
+train_harness.plan_fingerprint's ``sha256`` over the op sequence and its ``layout_sha256`` over the host-side plan contents the run
+path reads (arena size, workspace, parameter slices, zero list, piece offsets, backward ranges, attention buffers).  The cases:
+yolov3, yolov4 and yolov3-mobilenet at 64 x 64, batch 2, fp16 and fp32, the tiny cfgs, a slim-pruned cfg that trains through the
+channel-padded twin, the test harness's mini cfg, three attention plans, another shape, and yolov3 fp16 under each builder knob.
+tests/test_train_emulated.py::test_train_plan_ops_are_pinned holds the builder to it.
 
-The committed file was recorded at the last commit whose builder still had the side lane and the second workspace (both off by
-default), so it pins that the builder without them emits the same ops, descriptors, fixups and arena offsets.
+The committed file was recorded with engine/train.py of commit 47582ea ("Training backward on one stream: drop side lane and async
+reduce"), the last one whose builder was the single method TrainEngine._build_train_plan_: it pins that engine/train_plan.py emits the
+same ops, descriptors, fixups, arena offsets and plan contents.  With that commit's engine/train.py in place of today's, this script
+rewrites the file byte for byte.  (The ``sha256`` of the first seven rows goes back further: to the last builder that still had the
+side lane and the second workspace.)
 """
 import json
 import os
@@ -21,10 +28,10 @@ import train_harness as th  # noqa: E402
 
 def main():
     rows = []
-    for cfg, precision, attention in th.PLAN_CASES:
-        row = th.plan_fingerprint(cfg, precision, attention)
+    for case in th.PLAN_CASES:
+        row = th.plan_case_fingerprint(case)
         print(row)
-        del row['arena_need']       # reported, not pinned
+        del row['arena_need']       # reported; pinned through layout_sha256
         rows.append(row)
     out = os.path.join(HERE, 'train_plan_ops.json')
     with open(out, 'w') as fh:

@@ -675,17 +675,44 @@ def test_shortcut_whose_operand_is_a_concat_keeps_the_parts_gradients():
         os.unlink(path)
 
 
-@pytest.mark.parametrize('case', range(len(th.PLAN_CASES)), ids=['%s-%s%s' % (os.path.basename(c), p, '-attention' if a else '') for c, p, a in th.PLAN_CASES])
+@pytest.mark.parametrize('case', range(len(th.PLAN_CASES)), ids=[th.plan_case_id(c) for c in th.PLAN_CASES])
 def test_train_plan_ops_are_pinned(case):
     """What the plan builder hands the plan API - op names and kinds, every non-pointer descriptor field, which pointer fields are
-    null / patched by a fixup / fixed addresses, and every fixup with its slot and arena byte offset - against the digests recorded
-    with the builder that still carried the side lane and the second workspace (tests/golden/make_golden_train_plan.py).  The
-    plans are built only, never run; `arena_need` is not pinned (it shrank by the one 512-byte piece of the second workspace)."""
+    null / patched by a fixup / fixed addresses, and every fixup with its slot and arena byte offset (`sha256`) - and what it leaves
+    in the plan dict for the run path - arena size, workspace, parameter slices, zero list, piece offsets, backward ranges, attention
+    buffers (`layout_sha256`) - against the digests recorded with the builder that was one method of engine/train.py
+    (tests/golden/make_golden_train_plan.py).  The plans are built only, never run."""
     import json
     want = json.load(open(os.path.join(conftest.REPO, 'tests', 'golden', 'train_plan_ops.json')))[case]
-    cfg, precision, attention = th.PLAN_CASES[case]
-    assert (want['cfg'], want['precision'], want['attention']) == (cfg, precision, attention)
-    got = th.plan_fingerprint(cfg, precision, attention)
+    cfg, precision, attention = th.PLAN_CASES[case][:3]
+    assert (want['cfg'], want['precision'], want['attention'], want.get('options', {})) == \
+        (cfg, precision, attention, th.plan_case_options(th.PLAN_CASES[case]))
+    got = th.plan_case_fingerprint(th.PLAN_CASES[case])
     print(got)
     assert (got['n_fwd'], got['n_bwd']) == (want['n_fwd'], want['n_bwd'])
     assert got['sha256'] == want['sha256']
+    assert got['layout_sha256'] == want['layout_sha256']
+
+
+def test_sealed_gradient_buffer_refuses_a_writer(mini):
+    """Once a data gradient took the BatchNorm backward sums of a block, nothing may write that block's gradient buffer before its
+    own backward consumed it: `contribution_mode`, which every writer of a gradient buffer asks, raises at plan build."""
+    from engine.train import TrainEngine
+    from engine.train_plan import _TrainPlanBuilder
+    eng = TrainEngine(th.build(mini, 64), 'fp32', lib=fakelib.FakeLib())
+    eng.device = torch.device('cpu')
+    builder = _TrainPlanBuilder(eng, 2, 3, 64, 64, False)
+    builder.build()
+    assert builder.sealed == {}        # every seal was lifted by the backward of its block
+    own = [v for v in builder.values if v.kind == 'conv' and v.bn is not None and v.parent is None and v.ld == v.c_phys]
+    s, other = own[2], own[3]
+    assert s.gstorage is not other.gstorage
+    builder.sealed[id(s.gstorage)] = s
+    with pytest.raises(RuntimeError, match=r'probe writes the gradient buffer of block %d\b' % s.block):
+        builder.contribution_mode(s, True, 'probe')
+    assert builder.contribution_mode(other, True, 'probe') == 'acc'          # holds a contribution: accumulate
+    builder.initialised.discard(id(other.gstorage))
+    n_zero = len(builder.plan['zero_list'])
+    assert builder.contribution_mode(other, True, 'probe') == 'write'        # first full-width writer
+    assert builder.contribution_mode(other, True, 'probe') == 'acc'
+    assert len(builder.plan['zero_list']) == n_zero

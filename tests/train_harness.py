@@ -92,15 +92,96 @@ def engine_step(model, x, ws, precision, lib=None, device='cpu'):
 
 PLAN_CASES = [(cfg, precision, False) for cfg in ('yolov3/yolov3.cfg', 'yolov4/yolov4.cfg', 'yolov3-mobilenet/yolov3-mobilenet-coco.cfg')
               for precision in ('fp16', 'fp32')] + [('yolov3/yolov3.cfg', 'fp16', True)]
+# Further cases carry options after the three fields: size / batch, env (builder knobs, set around the build) and patch (attributes of
+# engine.train set around the build: _FUSED_DGRAD_MAX_CIN is read at import).  ``cfg`` is a path below cfg/, a path below the
+# repository (tests/golden/...) or one of the MINI_CFGS names.
+MINI_CFGS = {"mini_cfg_text()": 'leaky', "mini_cfg_text('mish')": 'mish'}
+_V3 = 'yolov3/yolov3.cfg'
+PLAN_CASES += [
+    ('yolov3tiny/yolov3-tiny.cfg', 'fp16', False),
+    ('yolov3tiny/yolov3-tiny-hand.cfg', 'fp16', False),
+    ('yolov4tiny/yolov4-tiny.cfg', 'fp16', False),
+    ('yolov4tiny/yolov4-tiny.cfg', 'fp32', False),
+    ('tests/golden/slim_prune_0.5_yolov3-mobilenet-coco.cfg', 'fp16', False),     # through the channel-padded twin
+    ("mini_cfg_text()", 'fp16', False),
+    ("mini_cfg_text('mish')", 'fp32', False),
+    ('yolov4/yolov4.cfg', 'fp16', True),
+    ('yolov3-mobilenet/yolov3-mobilenet-coco.cfg', 'fp16', True),
+    (_V3, 'fp16', False, dict(size=96, batch=1)),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_FUSE_DBN': '0'})),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_STEM_STATS': '0'})),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_STEM_BWD': '0'})),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_STEM_DGRAD': '0'})),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_TILE': '24'})),
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_TRAIN_SEGMENTS': '3'})),
+    # every stride-2 data gradient in four parity phases
+    (_V3, 'fp16', False, dict(env={'YOLO_HIP_STEM_DGRAD': '0'}, patch={'_FUSED_DGRAD_MAX_CIN': 0})),
+]
 
 
-def plan_fingerprint(cfg, precision, attention=False, size=64, batch=2):
-    """Build (never run) the training plan of ``cfg`` (a path below cfg/) on the host emulation and digest what the builder handed
-    the plan API.  Per op: log name, kind, every non-pointer field (arrays as bytes), per pointer field null / fixup / other, and
+def plan_case_options(case):
+    return dict(case[3]) if len(case) > 3 else {}
+
+
+def plan_case_id(case):
+    opts = plan_case_options(case)
+    words = [os.path.basename(case[0]), case[1]] + ['attention'] * bool(case[2])
+    words += ['%s%s' % (k, opts[k]) for k in ('size', 'batch') if k in opts]
+    words += ['%s=%s' % kv for k in ('env', 'patch') for kv in sorted(opts.get(k, {}).items())]
+    return '-'.join(words)
+
+
+def plan_case_fingerprint(case):
+    """``plan_fingerprint`` of one PLAN_CASES entry: resolves its cfg, applies its options, and reports the cfg under the
+    name the case gives it (the recorded rows hold no absolute path)."""
+    import engine.train
+    cfg, precision, attention = case[:3]
+    opts = plan_case_options(case)
+    patch = opts.pop('patch', {})
+    path, temp = cfg, None
+    if cfg in MINI_CFGS:
+        path = temp = write_cfg(mini_cfg_text(MINI_CFGS[cfg]))
+    elif cfg.startswith('tests/'):
+        path = os.path.join(conftest.REPO, cfg)
+    before = {k: getattr(engine.train, k) for k in patch}
+    try:
+        for k, val in patch.items():
+            setattr(engine.train, k, val)
+        row = plan_fingerprint(path, precision, attention, **opts)
+    finally:
+        for k, val in before.items():
+            setattr(engine.train, k, val)
+        if temp:
+            os.unlink(temp)
+    row['cfg'] = cfg
+    if len(case) > 3:
+        row['options'] = case[3]
+    return row
+
+
+def _plan_layout(plan):
+    """The host-side plan contents the run path reads, as plain numbers (pieces by index and arena offset)."""
+    out = dict(arena_need=plan['arena_need'], ws_floats=plan['ws_floats'], junk_n=plan['junk_n'], junk=plan['junk'],
+               head_shapes=[list(s) for s in plan['head_shapes']],
+               param_slices=[[off, n, list(shape)] for off, n, shape in plan['param_slices']],
+               zero_list=[[t.index, t.off] for t in plan['zero_list']],
+               storages=[len(plan['storages'])] + [t.off for t in plan['storages']],
+               segments=[[list(seg['values']), list(seg['ops']), list(seg['params']), list(seg['heads'])] for seg in plan['segments']])
+    if plan.get('kd_values'):
+        out['kd'] = [[plan[k].n, plan[k].off] for k in ('kd_maps', 'kd_G', 'kd_partials')] + [len(plan['kd_values'])]
+    return out
+
+
+def plan_fingerprint(cfg, precision, attention=False, size=64, batch=2, env=None):
+    """Build (never run) the training plan of ``cfg`` (a path below cfg/, or an absolute path) on the host emulation, with the
+    environment variables ``env`` set around the build, and digest what the builder handed the plan API.  ``sha256``, per op: log
+    name, kind, every non-pointer field (arrays as bytes), per pointer field null / fixup / other, and
     the sorted fixups (field offset, slot, byte offset) - the byte offsets pin the arena layout of every piece.  The emulation's
-    weight-gradient workspace queries answer a non-zero constant, so the weight gradients' workspace fixups are in the digest."""
+    weight-gradient workspace queries answer a non-zero constant, so the weight gradients' workspace fixups are in the digest.
+    ``layout_sha256``: what the plan dict itself tells the run path (``_plan_layout``)."""
     import ctypes as C
     import hashlib
+    import json
     import fakelib
     from engine.padded import make_train_engine
 
@@ -115,10 +196,19 @@ def plan_fingerprint(cfg, precision, attention=False, size=64, batch=2):
     torch.manual_seed(0)
     model = Darknet(os.path.join(conftest.PKG, 'cfg', cfg), (size, size)).train()
     shape = (batch, 3, size, size)
-    eng = make_train_engine(model, precision, shape, lib=lib)
-    eng = getattr(eng, 'inner', eng)
-    eng.attention = attention
-    plan = eng._cached_plan(eng._plan_key(shape))
+    before = {k: os.environ.get(k) for k in env or {}}
+    os.environ.update(env or {})
+    try:
+        eng = make_train_engine(model, precision, shape, lib=lib)
+        eng = getattr(eng, 'inner', eng)
+        eng.attention = attention
+        plan = eng._cached_plan(eng._plan_key(shape))
+    finally:
+        for k, val in before.items():
+            if val is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = val
     out = dict(cfg=cfg, precision=precision, attention=attention, arena_need=plan['arena_need'])
     h = hashlib.sha256()
     for side in ('fwd', 'bwd'):
@@ -138,6 +228,7 @@ def plan_fingerprint(cfg, precision, attention=False, size=64, batch=2):
             h.update(repr(sorted(fixups)).encode())
             h.update(b'\n')
     out['sha256'] = h.hexdigest()
+    out['layout_sha256'] = hashlib.sha256(json.dumps(_plan_layout(plan), sort_keys=True).encode()).hexdigest()
     return out
 
 

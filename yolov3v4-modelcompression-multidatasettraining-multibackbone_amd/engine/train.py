@@ -31,6 +31,9 @@ Depthwise blocks, squeeze-excite, max-pools (incl. SPP) and CSP group-split rout
 csrc/train.hip).  Graphs whose widths are not multiples of 8 (slim-pruned nets, GhostNet) train through the channel-padded twin
 of ``engine/padded.py``; what neither form covers (weighted shortcuts, grouped convs other than depthwise) raises
 NotImplementedError at plan build - ``models.Darknet`` has no eager fallback for training.
+
+The plans are built by ``_TrainPlanBuilder`` (``engine/train_plan.py``: one emitter per block kind and pass); this module keeps the
+engine, the arenas and the run path.
 """
 import ctypes as C
 import os
@@ -39,9 +42,7 @@ import torch
 import torch.nn as nn
 
 from . import hiplib
-from .hiplib import (ConvDesc, StemDesc, CopyDesc, AddDesc, BnStatsDesc, BnFinalizeDesc, BnActFwdDesc, BnBwdReduceDesc,
-                     BnBwdApplyDesc, WgradDesc, StemWgradDesc, StemBwdDesc, UpsampleBwdDesc, CastDesc, LayoutDesc, PoolDesc, PoolBwdDesc, PackItem, PackBatchDesc, DwDesc, SeDesc, DwWgradDesc,
-                     DwDgradDesc, SeBwdDesc, BnL1Row)
+from .hiplib import PackItem, BnL1Row
 from .plan import DarknetEngine, ALIGN_C, _round_up
 
 # stride-2 data gradients with at most this many input channels run as ONE four-phase pass (ups = 4: 16 tap-GEMMs instead of 9, dz read
@@ -353,9 +354,10 @@ class TrainEngine(DarknetEngine):
         # attention plans are built like the evaluation engine's feature_out plans: every conv block keeps its own output (no
         # shortcut / upsample fused into its store), and the next block's data gradient is never folded into the first block's
         # one-pass backward (that form does not materialise the gradient the injection lands in)
+        from .train_plan import _TrainPlanBuilder     # imports this module
         self.return_features = self._building_attention = bool(attention)
         try:
-            return self._build_train_plan_(N, Cin, H, W, bool(attention))
+            return _TrainPlanBuilder(self, N, Cin, H, W, bool(attention)).build()
         finally:
             self.return_features = self._building_attention = False
 
@@ -371,650 +373,6 @@ class TrainEngine(DarknetEngine):
         if not feats:
             raise NotImplementedError('HIP training path: the graph has no feature_out block')
         return feats
-
-    def _build_train_plan_(self, N, Cin, H, W, attention):
-        values, heads, outs = self._build_values(N, Cin, H, W)
-        self._check_supported(values)
-        self._place(values)
-        lib, dev, P = self.lib, self.device, hiplib.ptr
-        plan = dict(values=values, heads=heads, N=N, storages=[], fwd_ops=[], bwd_ops=[], zero_list=[], ws_floats=0,
-                    arena=self._arena, arena_refs=[], state=_PlanState(dev), bound=None)
-        fwd = plan['fwd'] = lib.yh_plan_create()
-        bwd = plan['bwd'] = lib.yh_plan_create()
-        if not fwd or not bwd:
-            raise MemoryError('yh_plan_create failed')
-        stats = plan['stats'] = _Arena()      # zeroed before every forward: BN sums
-        saved = plan['saved'] = _Arena()      # mean / invstd per BN (kept from forward to backward)
-        grads = plan['grads'] = _Arena()      # parameter gradients (zeroed before every backward)
-
-        def add(handle, log, desc, what):
-            idx = lib.yh_plan_add(handle, hiplib.OP_KIND[type(desc)], C.byref(desc), C.sizeof(desc))
-            if idx < 0:
-                hiplib.check(idx, 'yh_plan_add(%s)' % what)
-            log.append((what, desc))
-            for name, ctype in desc._fields_:
-                val = getattr(desc, name) if ctype is C.c_void_p else None
-                if val and val >> 62 == 1:          # a step buffer: becomes a fixup on the arena slot once the pieces are placed
-                    plan['arena_refs'].append((handle, idx, getattr(type(desc), name).offset, (val ^ _PIECE_TAG) >> _PIECE_SHIFT,
-                                               val & ((1 << _PIECE_SHIFT) - 1), what))
-            return idx
-
-        def fixup(handle, op, desc_type, field, slot):
-            hiplib.check(lib.yh_plan_add_fixup(handle, op, getattr(desc_type, field).offset, slot, 0), 'fixup')
-
-        def add_reduction(handle, log, desc, what):
-            """Reductions get the shared workspace (bound to SLOT_WS at run time) sized by the library's own query."""
-            query = lib.yh_conv2d_wgrad_workspace if isinstance(desc, WgradDesc) and not isinstance(desc, StemWgradDesc) \
-                else lib.yh_dw_wgrad_workspace if isinstance(desc, DwWgradDesc) else lib.yh_bn_reduce_workspace
-            need = int(query(C.byref(desc)))
-            desc.ws_floats = need
-            plan['ws_floats'] = max(plan['ws_floats'], need)
-            op = add(handle, log, desc, what)
-            if need:
-                fixup(handle, op, type(desc), 'ws', SLOT_WS)
-            return op
-
-        pieces = []
-
-        def alloc(shape, fp32=False):
-            """A step buffer: a piece of the engine's arena, which other plans overwrite between two steps of this one - nothing
-            may rely on what an earlier step (or the build) left in it."""
-            n = 1
-            for k in shape:
-                n *= int(k)
-            t = _Piece(self._arena, len(pieces), n, torch.float32 if fp32 else self.dtype)
-            pieces.append(t)
-            plan['storages'].append(t)
-            return t
-
-        def keep(n, dtype, zero=False):
-            """State the plan keeps for itself, outside the arena (counted in plan_bytes)."""
-            return plan['state'].tensor(n, dtype, zero)
-
-        def materialize(v):
-            if v.storage is not None:
-                return
-            if v.parent is not None:
-                materialize(v.parent)
-                v.storage, v.c_off, v.ld = v.parent.storage, v.parent.c_off + v.parent_off, v.parent.ld
-                v.gstorage = v.parent.gstorage
-            else:
-                v.storage = None if v.fp32 else alloc((N, v.H, v.W, v.c_phys))
-                v.gstorage = None if v.fp32 else alloc((N, v.H, v.W, v.c_phys))
-                v.c_off, v.ld = 0, v.c_phys
-
-        # ---- pass 1: buffers, parameter slots
-        kstep = self.kstep
-        pidx = 0
-        plan['param_slices'] = []   # (arena offset, numel, shape) in parameters() order
-        for v in values:
-            if v.kind == 'input':
-                continue
-            if v.kind == 'slice':   # a channel range of its source: same buffers, forward and gradient
-                materialize(v.src)
-                v.storage, v.gstorage, v.c_off, v.ld = v.src.storage, v.src.gstorage, v.src.c_off + v.first, v.src.ld
-                continue
-            materialize(v)
-            if v.kind == 'dw':
-                conv, bn = v.conv, v.bn
-                v.p_first = len(plan['param_slices'])
-                v.g_w = grads.reserve(conv.weight.numel())
-                plan['param_slices'].append((v.g_w, conv.weight.numel(), tuple(conv.weight.shape)))
-                v.g_b = None
-                if conv.bias is not None:
-                    v.g_b = grads.reserve(v.c_phys)
-                    plan['param_slices'].append((v.g_b, v.C, (v.C,)))
-                if bn is not None:
-                    v.g_gamma, v.g_beta = grads.reserve(v.C), grads.reserve(v.C)
-                    plan['param_slices'].append((v.g_gamma, v.C, (v.C,)))
-                    plan['param_slices'].append((v.g_beta, v.C, (v.C,)))
-                    v.s_sum, v.s_sumsq = stats.reserve(v.C), stats.reserve(v.C)
-                    v.s_mean, v.s_invstd = saved.reserve(v.C), saved.reserve(v.C)
-                v.tpack = dict(w=keep(v.k * v.k * v.c_phys, self.dtype),
-                               b=keep(v.c_phys, torch.float32))
-                v.plain = bn is None and v.act == LINEAR
-                v.z = None if v.plain else alloc((N, v.H, v.W, v.c_phys))
-                v.res, v.ups, v.Ho, v.Wo, v.fp32 = None, 1, v.H, v.W, False
-                continue
-            if v.kind == 'se':
-                v.p_first = len(plan['param_slices'])
-                v.g_w1 = grads.reserve(v.fc1.weight.numel())
-                plan['param_slices'].append((v.g_w1, v.fc1.weight.numel(), tuple(v.fc1.weight.shape)))
-                v.g_w2 = grads.reserve(v.fc2.weight.numel())
-                plan['param_slices'].append((v.g_w2, v.fc2.weight.numel(), tuple(v.fc2.weight.shape)))
-                for t in (v.fc1.weight, v.fc2.weight):
-                    if t.dtype != torch.float32 or not t.is_contiguous():
-                        raise NotImplementedError('HIP training path: parameters must be contiguous fp32 (master weights)')
-                v.pooled = alloc((N, v.c_phys), fp32=True)
-                v.gate = alloc((N, v.c_phys), fp32=True)
-                v.scratch = alloc((N, v.c_phys), fp32=True)
-                v.scratch2 = alloc((N, v.c_phys + 2 * v.fc1.weight.shape[0]), fp32=True)      # factors of the two weight gradients per image
-                continue
-            if v.kind != 'conv':
-                continue
-            conv, bn = v.conv, v.bn
-            taps = v.k * v.k
-            v.p_first = len(plan['param_slices'])
-            v.g_w = grads.reserve(conv.weight.numel())
-            plan['param_slices'].append((v.g_w, conv.weight.numel(), tuple(conv.weight.shape)))
-            v.g_b = None
-            if conv.bias is not None:
-                v.g_b = grads.reserve(v.c_phys)
-                plan['param_slices'].append((v.g_b, v.C, (v.C,)))
-            if bn is not None:
-                v.g_gamma, v.g_beta = grads.reserve(v.C), grads.reserve(v.C)
-                plan['param_slices'].append((v.g_gamma, v.C, (v.C,)))
-                plan['param_slices'].append((v.g_beta, v.C, (v.C,)))
-                v.s_sum, v.s_sumsq = stats.reserve(v.C), stats.reserve(v.C)
-                v.s_mean, v.s_invstd = saved.reserve(v.C), saved.reserve(v.C)
-            if v.src.kind == 'input':
-                cout_pad = _round_up(v.C, 32) if v.C % 32 == 0 else _round_up(v.C, 16)
-                v.tpack = dict(w=keep(taps * v.src.C * cout_pad, torch.float32),
-                               b=keep(cout_pad, torch.float32), cout_pad=cout_pad)
-            else:
-                cin_k = _round_up(v.src.c_phys, kstep)
-                m_pad = _round_up(v.c_phys, 128)
-                cout_k = _round_up(v.c_phys, kstep)          # dgrad: K runs over the output channels
-                dm_pad = _round_up(v.src.c_phys, 128)
-                v.tpack = dict(w=keep(m_pad * taps * cin_k, self.dtype),
-                               b=keep(m_pad, torch.float32), cin_k=cin_k, m_pad=m_pad,
-                               wt=None if v.stride == 2 else keep(dm_pad * taps * cout_k, self.dtype),
-                               cout_k=cout_k, dm_pad=dm_pad)
-                if self._dgrad_fused_into_stem(values, v):
-                    v.tpack['stem_fused'] = True
-                    v.tpack['wt'] = keep(dm_pad * taps * cout_k, self.dtype)
-                elif v.stride == 2 and 16 <= v.src.c_phys <= _FUSED_DGRAD_MAX_CIN and v.src.c_phys % 4 == 0:
-                    # few input channels: the data gradient is bound by reading dz and writing dx, so all four parity phases
-                    # run as ONE 2x2-tap GEMM with 4 * cin rows (16 tap-GEMMs instead of 9, but dz is read once, not four
-                    # times, and each workgroup writes whole rows of dx): yh_conv2d_fwd ups = 4
-                    v.tpack['fused_m_pad'] = _round_up(4 * v.src.c_phys, 128)
-                    v.tpack['wt_fused'] = keep(v.tpack['fused_m_pad'] * 4 * cout_k, self.dtype)
-                elif v.stride == 2:
-                    # parity (a, b) sees ((a + pad) // 2 + 1) x ((b + pad) // 2 + 1) taps
-                    v.tpack['phase_taps'] = [((a + v.pad) // 2 + 1, (b + v.pad) // 2 + 1) for a in (0, 1) for b in (0, 1)]
-                    v.tpack['wt_phase'] = [keep(dm_pad * th * tw * cout_k, self.dtype)
-                                           for th, tw in v.tpack['phase_taps']]
-            # z: the conv output before BN / activation.  Blocks with neither BN nor activation store straight to y.
-            v.plain = bn is None and v.act == LINEAR and v.res is None and v.ups == 1
-            if v.fp32:
-                if not v.plain:
-                    raise NotImplementedError('HIP training path: yolo-head conv with BN / activation / residual')
-                v.z = None
-            elif v.plain:
-                v.z = None
-            else:
-                v.z = alloc((N, v.Ho, v.Wo, v.c_phys))
-        plan['junk_n'] = max(v.c_phys for v in values if v.kind in ('conv', 'dw'))
-        plan['junk'] = grads.reserve(plan['junk_n'])
-        stats.allocate(plan['state'])
-        saved.allocate(plan['state'])
-        grads.allocate(plan['state'])
-        # one zero row serves every data gradient as its bias: as long as the longest m_pad among them, incl. the one-pass stride-2 form's
-        # 4 * cin rows (ADVICE r5: a narrow / pruned net whose widest conv input is <= 128 but that has a stride-2 conv with 33 .. 64
-        # inputs needs 256 there and failed at plan build)
-        # (it is read-only and its length does not depend on the input shape: the plan's own, outside the arena, so no step has to
-        # zero it again after another plan used the arena)
-        zero_bias = keep(max([max(_round_up(v.src.c_phys, 128), v.tpack.get('fused_m_pad', 0))
-                              for v in values if v.kind == 'conv' and v.src.kind != 'input'] + [128]), torch.float32, zero=True)
-        dz_elems = max(N * v.Ho * v.Wo * v.c_phys for v in values if v.kind in ('conv', 'dw'))
-        # one dz scratch, one stream: a side lane for the weight gradients and a reduce stream were measured and removed (DESIGN.md 3.3 (d), (e))
-        dz_buf = alloc((dz_elems,))
-        head_index = {id(h.src): k for k, h in enumerate(heads)}
-
-        raw, n_items = self._pack_items(plan)
-        plan['pack_table'] = keep(len(raw), torch.uint8, zero=True)
-        add(fwd, plan['fwd_ops'], PackBatchDesc(items=plan['pack_table'].data_ptr(), n_items=n_items), 'pack')
-
-        # ---- pass 2: forward ops
-        for v in values:
-            if v.kind == 'input':
-                continue
-            y = None if v.storage is None else P(v.storage, v.c_off)
-            if v.kind == 'conv':
-                pk, s = v.tpack, v.src
-                fused_stats = 0
-                direct = v.plain                     # conv epilogue writes the block output itself
-                zt = None if direct else v.z
-                if s.kind == 'input':
-                    d = StemDesc(x=None, w=P(pk['w']), bias=P(pk['b']), y=y if direct else P(zt), n=N, cin=s.C, h=s.H,
-                                 w_in=s.W, ho=v.Ho, wo=v.Wo, cout=v.c_phys, cout_pad=pk['cout_pad'], kh=v.k, kw=v.k,
-                                 stride=v.stride, pad=v.pad, ldy=v.ld if direct else v.c_phys, act=LINEAR, slope=0.0,
-                                 dtype=self.code, out_scale=0.0)
-                    if v.c_phys > pk['cout_pad'] or v.fp32:
-                        raise NotImplementedError('HIP training path: stem geometry')
-                    if v.bn is not None and not direct and os.environ.get('YOLO_HIP_STEM_STATS', '1') != '0':
-                        # the MFMA first-layer kernel also emits the BatchNorm partial sums of what it stores (no yh_bn_stats pass)
-                        fused_stats = int(lib.yh_conv2d_stem_stats_rows(C.byref(d)))
-                        if fused_stats:
-                            d.stats_ws_floats = fused_stats * 2 * v.c_phys
-                            plan['ws_floats'] = max(plan['ws_floats'], d.stats_ws_floats)
-                    op = add(fwd, plan['fwd_ops'], d, 'stem%d' % v.block)
-                    fixup(fwd, op, StemDesc, 'x', SLOT_INPUT)
-                    if fused_stats:
-                        fixup(fwd, op, StemDesc, 'stats_ws', SLOT_WS)
-                else:
-                    d = ConvDesc(x=P(s.storage, s.c_off), w=P(pk['w']), bias=P(pk['b']), res=None,
-                                 y=None if v.fp32 else (y if direct else P(zt)), n=N, h=s.H, w_in=s.W, cin=s.c_phys,
-                                 ho=v.Ho, wo=v.Wo, cout=v.c_phys, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=s.ld,
-                                 ldr=0, ldy=v.c_phys if (v.fp32 or not direct) else v.ld, cin_k=pk['cin_k'],
-                                 m_pad=pk['m_pad'], act=LINEAR, slope=0.0, ups=1, out_f32=1 if v.fp32 else 0,
-                                 dtype=self.code, tile=self.force_tile, acc_scale=0.0, out_scale=0.0)
-                    if v.bn is not None and not direct:
-                        # BatchNorm statistics ride in the conv epilogue: per-tile partial sums into the shared workspace
-                        fused_stats = int(lib.yh_conv2d_stats_rows(C.byref(d)))
-                        if fused_stats:
-                            d.stats_ws_floats = fused_stats * 2 * v.c_phys
-                            plan['ws_floats'] = max(plan['ws_floats'], d.stats_ws_floats)
-                    op = add(fwd, plan['fwd_ops'], d, 'conv%d' % v.block)
-                    if fused_stats:
-                        fixup(fwd, op, ConvDesc, 'stats_ws', SLOT_WS)
-                    if v.fp32:
-                        fixup(fwd, op, ConvDesc, 'y', SLOT_HEAD0 + head_index[id(v)])
-                if direct:
-                    continue
-                pixels = N * v.Ho * v.Wo
-                bn = v.bn
-                base = dict(z=P(zt), pixels=pixels, n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, ldz=v.c_phys, act=v.act,
-                            slope=v.slope, dtype=self.code, ups=v.ups)
-                if bn is not None:
-                    bnp = dict(gamma=P(bn.weight), beta=P(bn.bias), mean=saved.ptr(v.s_mean), invstd=saved.ptr(v.s_invstd),
-                               sum=stats.ptr(v.s_sum), sumsq=stats.ptr(v.s_sumsq), eps=float(bn.eps),
-                               momentum=float(bn.momentum))
-                    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-                        raise NotImplementedError('HIP training path: BatchNorm without momentum / running stats / affine')
-                    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
-                        if t.dtype != torch.float32 or not t.is_contiguous():
-                            raise NotImplementedError('HIP training path: BatchNorm tensors must be contiguous fp32')
-                    fused = bool(fused_stats)
-                    if not fused:
-                        add_reduction(fwd, plan['fwd_ops'], BnStatsDesc(**base, **bnp), 'bnstat%d' % v.block)
-                    fin = BnFinalizeDesc(**base, **bnp, running_mean=P(bn.running_mean), running_var=P(bn.running_var),
-                                         nparts=fused_stats if fused else 0, ws_floats=(fused_stats * 2 * v.c_phys) if fused else 0)
-                    op = add(fwd, plan['fwd_ops'], fin, 'bnfin%d' % v.block)
-                    if fused:
-                        fixup(fwd, op, BnFinalizeDesc, 'ws', SLOT_WS)
-                else:
-                    bnp = dict()
-                v.bn_args = (base, bnp)
-                add(fwd, plan['fwd_ops'],
-                    BnActFwdDesc(**base, **bnp, out=y, ldo=v.ld, res=None if v.res is None else P(v.res.storage, v.res.c_off),
-                                 ldr=0 if v.res is None else v.res.ld), 'bnact%d' % v.block)
-            elif v.kind == 'dw':
-                s, pk, bn = v.src, v.tpack, v.bn
-                zt = None if v.plain else v.z
-                add(fwd, plan['fwd_ops'],
-                    DwDesc(x=P(s.storage, s.c_off), w=P(pk['w']), bias=P(pk['b']), y=y if v.plain else P(zt), n=N, h=s.H, w_in=s.W,
-                           c=s.c_phys, ho=v.H, wo=v.W, k=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, ldy=v.ld if v.plain else v.c_phys,
-                           act=LINEAR, slope=0.0, dtype=self.code), 'dw%d' % v.block)
-                if not v.plain:
-                    pixels = N * v.H * v.W
-                    base = dict(z=P(zt), pixels=pixels, n=N, h=v.H, w_in=v.W, c=v.c_phys, ldz=v.c_phys, act=v.act, slope=v.slope,
-                                dtype=self.code, ups=1)
-                    bnp = dict()
-                    if bn is not None:
-                        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-                            raise NotImplementedError('HIP training path: BatchNorm without momentum / running stats / affine')
-                        bnp = dict(gamma=P(bn.weight), beta=P(bn.bias), mean=saved.ptr(v.s_mean), invstd=saved.ptr(v.s_invstd),
-                                   sum=stats.ptr(v.s_sum), sumsq=stats.ptr(v.s_sumsq), eps=float(bn.eps), momentum=float(bn.momentum))
-                        add_reduction(fwd, plan['fwd_ops'], BnStatsDesc(**base, **bnp), 'bnstat%d' % v.block)
-                        add(fwd, plan['fwd_ops'], BnFinalizeDesc(**base, **bnp, running_mean=P(bn.running_mean),
-                                                                 running_var=P(bn.running_var)), 'bnfin%d' % v.block)
-                    v.bn_args = (base, bnp)
-                    add(fwd, plan['fwd_ops'], BnActFwdDesc(**base, **bnp, out=y, ldo=v.ld), 'bnact%d' % v.block)
-            elif v.kind == 'se':
-                s = v.src
-                add(fwd, plan['fwd_ops'],
-                    SeDesc(x=P(s.storage, s.c_off), y=y, w1=P(v.fc1.weight), w2=P(v.fc2.weight), pooled=P(v.pooled), gate=P(v.gate),
-                           ch_map=None, n=N, h=s.H, w_in=s.W, c=v.C, c_phys=v.c_phys, cr=v.fc1.weight.shape[0], ldx=s.ld, ldy=v.ld,
-                           dtype=self.code), 'se%d' % v.block)
-            elif v.kind == 'pool':
-                s = v.src
-                add(fwd, plan['fwd_ops'], PoolDesc(x=P(s.storage, s.c_off), y=y, n=N, h=s.H, w_in=s.W, c=s.c_phys, ho=v.H, wo=v.W,
-                                                   k=v.k, stride=v.stride, pad_lo=v.pad_lo, edge_zero=v.edge_zero, ldx=s.ld,
-                                                   ldy=v.ld, dtype=self.code), 'pool%d' % v.block)
-            elif v.kind == 'copy':
-                s = v.src
-                add(fwd, plan['fwd_ops'], CopyDesc(x=P(s.storage, s.c_off), y=y, n=N, h=s.H, w_in=s.W, c=s.c_phys, ups=v.ups,
-                                                   ldx=s.ld, ldy=v.ld, dtype=self.code), 'ups%d' % v.block)
-            elif v.kind == 'add':
-                add(fwd, plan['fwd_ops'], AddDesc(a=P(v.a.storage, v.a.c_off), b=P(v.b.storage, v.b.c_off), y=y,
-                                                  pixels=N * v.H * v.W, c=v.c_phys, lda=v.a.ld, ldb=v.b.ld, ldy=v.ld,
-                                                  dtype=self.code), 'add%d' % v.block)
-            elif v.kind == 'concat':
-                for s, off, inplace in v.parts:
-                    if not inplace:
-                        add(fwd, plan['fwd_ops'], CopyDesc(x=P(s.storage, s.c_off), y=P(v.storage, v.c_off + off), n=N, h=s.H,
-                                                           w_in=s.W, c=s.c_phys, ups=1, ldx=s.ld, ldy=v.ld, dtype=self.code),
-                            'cat%d' % v.block)
-
-        # ---- pass 3: backward ops.  A gradient storage's first writer must cover it entirely; otherwise the
-        # storage is zeroed before the backward plan runs and every contribution accumulates.
-        initialised = set()
-        if attention:
-            # Feature distillation injects into the gradient of every feature value BEFORE the first backward op runs (one place:
-            # backward_segment of the last range).  So these buffers start as zeros and every contribution accumulates - also the
-            # ones that would otherwise have been the first, full-width write; a concat buffer one of them is produced into is zeroed
-            # as a whole, and the injection touches that value's lanes only.  The fusions that take a block's BatchNorm backward sums
-            # while completing its dy (completes_bn_block) stay on: they reduce the values they STORE, residual accumulate
-            # included, and the injection is already part of what they accumulate onto.
-            feats = plan['kd_values'] = self._attention_values(outs)
-            for u in feats:
-                if id(u.gstorage) not in initialised:
-                    initialised.add(id(u.gstorage))
-                    plan['zero_list'].append(u.gstorage)
-        # gradient buffers addressed by more than one value (a concat and the parts produced into it, a tensor and its channel
-        # slices): the residual-gradient aliasing below re-points ONE value's buffer and must leave these alone
-        holders = {}
-        for u in values:
-            if getattr(u, 'gstorage', None) is not None:
-                holders[id(u.gstorage)] = holders.get(id(u.gstorage), 0) + 1
-
-        # Who reads each value (by identity), in forward order: the backward runs over `values` in reverse, so the LAST contribution to
-        # a value's gradient comes from its consumer with the smallest index.  When that consumer is a 1x1 / stride-1 conv whose data
-        # gradient the library can run on its persistent kernel, the gradient it completes belongs to a BatchNorm block whose
-        # backward sums (sum g, sum g xhat) can be taken by that very launch - it has the finished dy rows in registers and reads z
-        # on top - instead of by a reduction pass over dy and z (yh_conv_desc.bwd_z, round 6; YOLO_HIP_FUSE_DBN=0 switches it off).
-        index = {id(u): i for i, u in enumerate(values)}
-        consumers = {}
-        for u in values:
-            ins = [getattr(u, 'src', None), getattr(u, 'res', None), getattr(u, 'a', None), getattr(u, 'b', None)]
-            ins += [part[0] for part in getattr(u, 'parts', None) or []]
-            for t in ins:
-                if t is not None and id(t) in index:
-                    consumers.setdefault(id(t), []).append(u)
-        fuse_dbn = os.environ.get('YOLO_HIP_FUSE_DBN', '1') != '0'
-
-        def completes_bn_block(v, s):
-            """conv `v` (1x1 / stride 1) writes the last contribution to grad(s), s a conv with BatchNorm whose gradient buffer is its own."""
-            if not fuse_dbn or v.k != 1 or v.stride != 1 or v.pad != 0 or s.kind != 'conv' or s.bn is None or s.plain or s.fp32 or s.ups != 1:
-                return False
-            if s.src.kind == 'input' or getattr(s, 'parent', None) is not None or s.c_off != 0 or s.ld != s.c_phys:
-                return False
-            if getattr(s, 'z', None) is None or not hasattr(s, 'bn_args'):
-                return False
-            return min(index[id(u)] for u in consumers.get(id(s), [v])) == index[id(v)]
-
-        def contribution_mode(t, full_width):
-            key = id(t.gstorage)
-            if key in initialised:
-                return 'acc'
-            initialised.add(key)
-            if full_width and t.c_off == 0 and t.ld == t.c_phys:
-                return 'write'
-            plan['zero_list'].append(t.gstorage)
-            return 'acc'
-
-        def gptr(t):
-            return P(t.gstorage, t.c_off)
-
-        def contribute(t, src_ptr, src_ld, pixels_hw, what):
-            """grad(t) (+)= rows at src_ptr (same spatial size and channel count as t)."""
-            mode = contribution_mode(t, True)
-            if mode == 'write':
-                add(bwd, plan['bwd_ops'], CopyDesc(x=src_ptr, y=gptr(t), n=N, h=t.H, w_in=t.W, c=t.c_phys, ups=1, ldx=src_ld,
-                                                   ldy=t.ld, dtype=self.code), what)
-            else:
-                add(bwd, plan['bwd_ops'], AddDesc(a=gptr(t), b=src_ptr, y=gptr(t), pixels=N * t.H * t.W, c=t.c_phys, lda=t.ld,
-                                                  ldb=src_ld, ldy=t.ld, dtype=self.code), what)
-
-        def has_grad(t):
-            return t.fp32 or id(t.gstorage) in initialised
-
-        bwd_pos = {}   # value -> index of its first backward op (ops of value i span [pos[i], pos[i-1]) in emission order)
-        for v in reversed(values):
-            bwd_pos[id(v)] = len(plan['bwd_ops'])
-            if v.kind == 'input':
-                continue
-            if v.kind == 'concat':
-                if not has_grad(v):
-                    continue
-                for s, off, inplace in v.parts:
-                    if not inplace:
-                        contribute(s, P(v.gstorage, v.c_off + off), v.ld, None, 'dcat%d' % v.block)
-                continue
-            if v.kind == 'add':
-                if has_grad(v):
-                    contribute(v.a, gptr(v), v.ld, None, 'dadd%d' % v.block)
-                    contribute(v.b, gptr(v), v.ld, None, 'dadd%d' % v.block)
-                continue
-            if v.kind == 'slice':
-                continue   # contributions to the slice were written straight into the source's gradient buffer
-            if v.kind == 'se':
-                if has_grad(v):
-                    s = v.src
-                    mode = contribution_mode(s, True)
-                    hw = s.H * s.W
-                    add(bwd, plan['bwd_ops'],
-                        SeBwdDesc(x=P(s.storage, s.c_off), dy=gptr(v), dx=gptr(s), w1=P(v.fc1.weight), w2=P(v.fc2.weight),
-                                  pooled=P(v.pooled), gate=P(v.gate), dw1=grads.ptr(v.g_w1), dw2=grads.ptr(v.g_w2), scratch=P(v.scratch),
-                                  scratch2=P(v.scratch2), scratch2_floats=v.scratch2.numel(),
-                                  n=N, h=s.H, w_in=s.W, c=v.c_phys, cr=v.fc1.weight.shape[0], ldx=s.ld, lddy=v.ld, lddx=s.ld,
-                                  accumulate=1 if mode == 'acc' else 0, dtype=self.code), 'dse%d' % v.block)
-                continue
-            if v.kind == 'dw':
-                if not has_grad(v):
-                    continue
-                s, pk = v.src, v.tpack
-                pixels = N * v.H * v.W
-                dyp, lddy = gptr(v), v.ld
-                if v.plain:
-                    dzp, lddz = dyp, lddy
-                else:
-                    dzp, lddz = P(dz_buf), v.c_phys
-                    base, bnp = v.bn_args
-                    if v.bn is not None:
-                        acc = dict(bnp, sum=grads.ptr(v.g_beta), sumsq=grads.ptr(v.g_gamma))
-                    else:
-                        acc = dict(sum=grads.ptr(v.g_b if v.g_b is not None else self._junk(plan, grads, v.c_phys)),
-                                   sumsq=grads.ptr(self._junk(plan, grads, v.c_phys)))
-                    add_reduction(bwd, plan['bwd_ops'], BnBwdReduceDesc(**base, **acc, dy=dyp, lddy=lddy), 'dbn%d' % v.block)
-                    add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys), 'dbnx%d' % v.block)
-                geo = dict(n=N, h=s.H, w_in=s.W, c=v.c_phys, ho=v.H, wo=v.W, k=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, lddz=lddz,
-                           dtype=self.code)
-                add_reduction(bwd, plan['bwd_ops'], DwWgradDesc(x=P(s.storage, s.c_off), dz=dzp, dw=grads.ptr(v.g_w), lddx=0, accumulate=0, **geo),
-                              'dwwgrad%d' % v.block)
-                if s.kind != 'input':
-                    mode = contribution_mode(s, True)
-                    add(bwd, plan['bwd_ops'], DwDgradDesc(dz=dzp, w=P(pk['w']), dx=gptr(s), lddx=s.ld,
-                                                          accumulate=1 if mode == 'acc' else 0, **geo), 'dwdgrad%d' % v.block)
-                continue
-            if v.kind == 'pool':
-                if has_grad(v):
-                    s = v.src
-                    contribution_mode(s, False)   # scatter-add: the target must hold zeros or an earlier contribution
-                    add(bwd, plan['bwd_ops'],
-                        PoolBwdDesc(x=P(s.storage, s.c_off), dy=gptr(v), dx=gptr(s), n=N, h=s.H, w_in=s.W, c=s.c_phys, ho=v.H,
-                                    wo=v.W, k=v.k, stride=v.stride, pad_lo=v.pad_lo, edge_zero=v.edge_zero, ldx=s.ld, lddy=v.ld,
-                                    lddx=s.ld, dtype=self.code), 'dpool%d' % v.block)
-                continue
-            if v.kind == 'copy':
-                if has_grad(v):
-                    s = v.src
-                    if contribution_mode(s, True) == 'write':
-                        add(bwd, plan['bwd_ops'], UpsampleBwdDesc(x=gptr(v), y=gptr(s), n=N, h=s.H, w_in=s.W, c=s.c_phys, big_h=2 * s.H, big_w=2 * s.W,
-                                                                  ldx=v.ld, ldy=s.ld, dtype=self.code), 'dups%d' % v.block)
-                    else:
-                        tmp = alloc((N, s.H, s.W, s.c_phys))
-                        add(bwd, plan['bwd_ops'], UpsampleBwdDesc(x=gptr(v), y=P(tmp), n=N, h=s.H, w_in=s.W, c=s.c_phys, big_h=2 * s.H, big_w=2 * s.W,
-                                                                  ldx=v.ld, ldy=s.c_phys, dtype=self.code), 'dups%d' % v.block)
-                        add(bwd, plan['bwd_ops'], AddDesc(a=gptr(s), b=P(tmp), y=gptr(s), pixels=N * s.H * s.W, c=s.c_phys,
-                                                          lda=s.ld, ldb=s.c_phys, ldy=s.ld, dtype=self.code), 'dups%d' % v.block)
-                continue
-            if v.kind != 'conv':
-                raise NotImplementedError('HIP training path: backward of %s' % v.kind)
-            if not has_grad(v):
-                continue                      # dead branch: its parameters get zero gradients
-            s, pk = v.src, v.tpack
-            pixels = N * v.Ho * v.Wo
-            dzp, lddz = P(dz_buf), v.c_phys
-            if v.fp32:                        # head: fp32 gradient from autograd -> dtype
-                op = add(bwd, plan['bwd_ops'], CastDesc(x=None, y=dzp, pixels=pixels, c=v.c_phys, ldx=v.c_phys, ldy=v.c_phys,
-                                                        dtype=self.code), 'dhead%d' % v.block)
-                fixup(bwd, op, CastDesc, 'x', SLOT_HEAD0 + head_index[id(v)])
-                if v.g_b is not None:         # bias gradient = sum over pixels of dz
-                    add_reduction(bwd, plan['bwd_ops'],
-                        BnBwdReduceDesc(z=dzp, dy=dzp, pixels=pixels, n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, ldz=v.c_phys,
-                                        lddy=v.c_phys, act=LINEAR, slope=0.0, dtype=self.code, ups=1,
-                                        sum=grads.ptr(v.g_b), sumsq=grads.ptr(self._junk(plan, grads, v.c_phys))),
-                        'dbias%d' % v.block)
-            else:
-                dyp, lddy = gptr(v), v.ld
-                if v.ups == 2:
-                    small = alloc((N, v.Ho, v.Wo, v.c_phys))
-                    add(bwd, plan['bwd_ops'], UpsampleBwdDesc(x=dyp, y=P(small), n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, big_h=2 * v.Ho, big_w=2 * v.Wo, ldx=lddy,
-                                                              ldy=v.c_phys, dtype=self.code), 'dups%d' % v.block)
-                    dyp, lddy = P(small), v.c_phys
-                if v.res is not None:
-                    t = v.res
-                    own = lambda u: u.parent is None and u.c_off == 0 and u.ld == u.c_phys and holders.get(id(u.gstorage), 0) == 1
-                    if (id(t.gstorage) not in initialised and v.ups == 1 and own(t) and own(v) and not t.fp32
-                            and (t.H, t.W, t.c_phys) == (v.H, v.W, v.c_phys) and not getattr(t, 'galias', False)):
-                        # first contribution to the residual source is dy itself: share the buffer instead of copying it.
-                        # Later contributions (the data gradient of the source's other consumer) accumulate in place, after
-                        # this block's backward has consumed dy.
-                        plan['storages'] = [u for u in plan['storages'] if u is not t.gstorage]   # free the unused buffer
-                        t.gstorage, t.galias = v.gstorage, True
-                    else:
-                        contribute(t, dyp, lddy, None, 'dres%d' % v.block)
-                if v.plain:                   # no BN, linear: dz is dy itself
-                    dzp, lddz = dyp, lddy
-                    if v.g_b is not None:
-                        add_reduction(bwd, plan['bwd_ops'],
-                            BnBwdReduceDesc(z=dyp, dy=dyp, pixels=pixels, n=N, h=v.Ho, w_in=v.Wo, c=v.c_phys, ldz=lddy,
-                                            lddy=lddy, act=LINEAR, slope=0.0, dtype=self.code, ups=1, sum=grads.ptr(v.g_b),
-                                            sumsq=grads.ptr(self._junk(plan, grads, v.c_phys))), 'dbias%d' % v.block)
-                else:
-                    base, bnp = v.bn_args
-                    base = dict(base, ups=1)
-                    if v.bn is not None:
-                        acc = dict(bnp, sum=grads.ptr(v.g_beta), sumsq=grads.ptr(v.g_gamma))
-                    else:                     # activation without BN: z already holds the bias
-                        acc = dict(sum=grads.ptr(v.g_b if v.g_b is not None else self._junk(plan, grads, v.c_phys)),
-                                   sumsq=grads.ptr(self._junk(plan, grads, v.c_phys)))
-                    if s.kind == 'input' and self._stem_bwd_fused(v, s):
-                        # first block: BatchNorm backward + weight gradient as ONE pass over dy and z (csrc/stem_bwd.hip) - its dz
-                        # has no other reader (no data gradient into the image), so it is never written
-                        sd = StemBwdDesc(x=None, dy=dyp, z=base['z'], gamma=bnp['gamma'], beta=bnp['beta'], mean=bnp['mean'],
-                                         invstd=bnp['invstd'], dgamma=grads.ptr(v.g_gamma), dbeta=grads.ptr(v.g_beta),
-                                         dw=grads.ptr(v.g_w), n=N, cin=s.C, h=s.H, w_in=s.W, cout=v.c_phys, lddy=lddy,
-                                         ldz=v.c_phys, act=v.act, slope=v.slope)
-                        for key, val in getattr(v, 'fused_dgrad', {}).items():
-                            setattr(sd, key, val)
-                        need = int(lib.yh_stem_bwd_workspace(C.byref(sd)))
-                        if need <= 0:
-                            raise RuntimeError('yh_stem_bwd_workspace rejected a geometry _stem_bwd_fused accepted')
-                        sd.ws_floats = need
-                        plan['ws_floats'] = max(plan['ws_floats'], need)
-                        op = add(bwd, plan['bwd_ops'], sd, ('stembwd%d' if not getattr(v, 'fused_dgrad', None) else 'stembwd_dgrad%d') % v.block)
-                        fixup(bwd, op, StemBwdDesc, 'ws', SLOT_WS)
-                        fixup(bwd, op, StemBwdDesc, 'x', SLOT_INPUT)
-                        continue
-                    if not getattr(v, 'dbn_done', False):     # else: the launch that completed dy took the sums (see dgrad below)
-                        add_reduction(bwd, plan['bwd_ops'], BnBwdReduceDesc(**base, **acc, dy=dyp, lddy=lddy), 'dbn%d' % v.block)
-                    add(bwd, plan['bwd_ops'], BnBwdApplyDesc(**base, **acc, dy=dyp, lddy=lddy, out=dzp, ldo=v.c_phys), 'dbnx%d' % v.block)
-            # weight gradient
-            if s.kind == 'input':
-                # the image as NHWC dtype with 8 channels (3..7 zero): the first layer then uses the MFMA wgrad kernel
-                img = alloc((N, s.H, s.W, ALIGN_C))
-                op = add(bwd, plan['bwd_ops'], LayoutDesc(x=None, y=P(img), n=N, c=s.C, h=s.H, w_in=s.W, c_pad=ALIGN_C, ldy=ALIGN_C,
-                                                          dtype=self.code), 'image%d' % v.block)
-                fixup(bwd, op, LayoutDesc, 'x', SLOT_INPUT)
-                add_reduction(bwd, plan['bwd_ops'],
-                              WgradDesc(x=P(img), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=ALIGN_C, ho=v.Ho, wo=v.Wo,
-                                        cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=ALIGN_C, lddz=lddz,
-                                        dtype=self.code, splits=0, cin_w=s.C), 'wgrad%d' % v.block)
-                continue
-            add_reduction(bwd, plan['bwd_ops'],
-                          WgradDesc(x=P(s.storage, s.c_off), dz=dzp, dw=grads.ptr(v.g_w), n=N, h=s.H, w_in=s.W, cin=s.C, ho=v.Ho,
-                                    wo=v.Wo, cout=v.C, kh=v.k, kw=v.k, stride=v.stride, pad=v.pad, ldx=s.ld, lddz=lddz,
-                                    dtype=self.code, splits=0), 'wgrad%d' % v.block)
-            # data gradient into grad(src)
-            mode = contribution_mode(s, True)
-            common = dict(bias=P(zero_bias), n=N, cin=v.c_phys, cout=s.c_phys, stride=1, ldx=lddz, ldr=s.ld if mode == 'acc' else 0,
-                          ldy=s.ld, cin_k=pk['cout_k'], m_pad=pk['dm_pad'], act=LINEAR, slope=0.0, out_f32=0, dtype=self.code,
-                          tile=self.force_tile if self.force_tile < 40 else 0, acc_scale=0.0, out_scale=0.0)
-            if pk.get('stem_fused'):
-                # no launch: the first block's backward computes this data gradient from dz on the fly (yh_stem_bwd dz1 / w1) and
-                # never materialises it.  dz stays valid until then: the first block writes no dz of its own.
-                if mode != 'write':
-                    raise RuntimeError('fused first-block data gradient must be the only contribution to its gradient')
-                s.fused_dgrad = dict(dz1=dzp, lddz1=lddz, w1=P(pk['wt']), h1=v.Ho, w1_in=v.Wo, k1=v.c_phys, k1_pad=pk['cout_k'])
-            elif v.stride == 2 and 'wt_fused' in pk:
-                fused = dict(common, cout=4 * s.c_phys, m_pad=pk['fused_m_pad'])
-                if zero_bias.numel() < pk['fused_m_pad']:
-                    raise RuntimeError('zero bias row is shorter than the fused data-gradient image')
-                add(bwd, plan['bwd_ops'],
-                    ConvDesc(x=dzp, w=P(pk['wt_fused']), res=gptr(s) if mode == 'acc' else None, y=gptr(s), h=v.Ho, w_in=v.Wo,
-                             ho=(s.H + 1) // 2, wo=(s.W + 1) // 2, kh=2, kw=2, pad=0, ups=4, y_h=s.H, y_w=s.W, **fused),
-                    'dgrad%d' % v.block)
-            elif v.stride == 2:
-                # input pixels of parity (a, b) only see the taps r = a + pad - 2t, s = b + pad - 2u: four small
-                # correlations of dz scattered onto every other pixel, 9 tap-GEMMs in total (a dilated pass runs 36)
-                for (a, b), (th, tw), img in zip(((0, 0), (0, 1), (1, 0), (1, 1)), pk['phase_taps'], pk['wt_phase']):
-                    hp, wp = (s.H - a + 1) // 2, (s.W - b + 1) // 2
-                    if hp <= 0 or wp <= 0:
-                        continue
-                    add(bwd, plan['bwd_ops'],
-                        ConvDesc(x=dzp, w=P(img), res=gptr(s) if mode == 'acc' else None, y=gptr(s), h=v.Ho, w_in=v.Wo, ho=hp, wo=wp,
-                                 kh=th, kw=tw, pad=0, ups=3, y_h=s.H, y_w=s.W, y_off_h=a, y_off_w=b, **common),
-                        'dgrad%d' % v.block)
-            else:
-                dg = ConvDesc(x=dzp, w=P(pk['wt']), res=gptr(s) if mode == 'acc' else None, y=gptr(s), h=v.Ho, w_in=v.Wo, ho=s.H,
-                              wo=s.W, kh=v.k, kw=v.k, pad=v.k - 1 - v.pad, ups=1, **common)
-                rows = 0
-                if completes_bn_block(v, s):
-                    sbase, sbnp = s.bn_args
-                    for key, val in dict(bwd_z=sbase['z'], bwd_ldz=s.c_phys, bwd_act=s.act, bwd_slope=s.slope, bwd_gamma=sbnp['gamma'],
-                                         bwd_beta=sbnp['beta'], bwd_mean=sbnp['mean'], bwd_invstd=sbnp['invstd']).items():
-                        setattr(dg, key, val)
-                    rows = int(lib.yh_conv2d_bwd_stats_rows(C.byref(dg)))
-                    if rows <= 0:
-                        for key in ('bwd_z', 'bwd_gamma', 'bwd_beta', 'bwd_mean', 'bwd_invstd'):
-                            setattr(dg, key, None)
-                if rows > 0:
-                    dg.stats_ws_floats = rows * 2 * s.c_phys
-                    plan['ws_floats'] = max(plan['ws_floats'], dg.stats_ws_floats)
-                op = add(bwd, plan['bwd_ops'], dg, 'dgrad%d' % v.block)
-                if rows > 0:
-                    # the rows it leaves in the shared workspace are added into dbeta / dgamma of `s` right away (the workspace is
-                    # free game for the next op); s's own backward then starts at its apply pass
-                    fixup(bwd, op, ConvDesc, 'stats_ws', SLOT_WS)
-                    sacc = dict(sbnp, sum=grads.ptr(s.g_beta), sumsq=grads.ptr(s.g_gamma))
-                    add_reduction(bwd, plan['bwd_ops'],
-                                  BnBwdReduceDesc(**dict(sbase, ups=1), **sacc, dy=gptr(s), lddy=s.ld, nparts=rows), 'dbn%d' % s.block)
-                    s.dbn_done = True
-        plan['head_shapes'] = [(N, h.src.H, h.src.W, h.src.c_phys) for h in heads]
-        plan['segments'] = self._make_segments(plan, values, heads, bwd_pos)
-        if attention:
-            # maps, G = p_s - p_t and the KL row partials are pieces of the step arena like every other step buffer: a reservation
-            # over all shapes covers them (train_stats' arena_bytes), the two tables are the plan's own (plan_bytes)
-            from . import kd
-            total = sum(N * u.H * u.W for u in feats)
-            sink = plan['kd_sink'] = kd.KdSink()
-            sink.lib = self.lib
-            raw, sink.n_kl_rows = kd.kl_rows([(N, u.H, u.W) for u in feats])
-            plan['kd_maps'], plan['kd_G'] = alloc((total,), fp32=True), alloc((total,), fp32=True)
-            plan['kd_partials'] = alloc((max(sink.n_kl_rows, 4),), fp32=True)
-            sink.kl_table = keep(len(raw), torch.uint8)
-            sink.kl_table.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-            plan['kd_table'] = keep(len(feats) * C.sizeof(hiplib.KdRow), torch.uint8, zero=True)
-            plan['kd_one'] = keep(1, torch.float32, zero=True).fill_(1.0)
-        plan['ws'] = alloc((max(plan['ws_floats'], 4),), fp32=True)
-        # place the pieces that are still in use (the residual-gradient aliasing above dropped some) and turn every pointer into
-        # them into a fixup on the arena slot: the plan holds offsets, `_bind` gives it the arena's address
-        need = 0
-        for t in plan['storages']:
-            t.off = need
-            need += _round_up(t.nbytes(), ARENA_ALIGN)
-        plan['arena_need'] = need
-        for handle, op, field, index, inner, what in plan['arena_refs']:
-            t = pieces[index]
-            if t.off is None or inner >= max(t.nbytes(), 1):
-                raise RuntimeError('%s points into a step buffer the plan does not keep' % what)
-            hiplib.check(lib.yh_plan_add_fixup(handle, op, field, SLOT_ARENA, t.off + inner), 'fixup')
-        del plan['arena_refs']
-        # what stays per plan: statistics, saved, gradient arenas, pack table, zero bias row and the weight images
-        return plan
 
     def _bind(self, plan):
         """Give the plan the arena's current address (after its build, and again after the arena grew)."""
@@ -1035,46 +393,6 @@ class TrainEngine(DarknetEngine):
                       c_off=u.c_off) for u in plan['kd_values']])
             assert all((base + u.storage.off) % 16 == 0 and (u.c_off * esz) % 16 == 0 for u in plan['kd_values'])
             plan['kd_table'].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-
-    def _stem_bwd_fused(self, v, s):
-        """The one-pass backward of the first block applies: fp16 step, 3x3 / stride 1 / pad 1 on a 1- or 3-channel image, 16 or
-        32 output channels, BatchNorm + activation, nothing fused into its store (YOLO_HIP_STEM_BWD=0: the four-launch form)."""
-        if os.environ.get('YOLO_HIP_STEM_BWD', '1') == '0':
-            return False
-        return (self.code == hiplib.YH_F16 and v.bn is not None and v.k == 3 and v.stride == 1 and v.pad == 1 and s.C in (1, 3)
-                and v.c_phys in (16, 32) and v.C == v.c_phys and v.ups == 1 and v.res is None and v.conv.bias is None)
-
-    def _dgrad_fused_into_stem(self, values, v):
-        """conv `v` is the ONLY consumer of the first block, a 3x3 / stride 2 / pad 1 conv with 64 output channels on its 32
-        channels, and the first block takes the one-pass backward: then v's data gradient is computed inside that pass
-        (YOLO_HIP_STEM_DGRAD=0 keeps it a launch of its own)."""
-        s = v.src
-        if os.environ.get('YOLO_HIP_STEM_DGRAD', '1') == '0':
-            return False
-        if self._building_attention:      # the first block's dy takes an injection: it has to exist as a buffer
-            return False
-        if v.kind != 'conv' or s.kind != 'conv' or s.src.kind != 'input' or not self._stem_bwd_fused(s, s.src):
-            return False
-        if not (v.k == 3 and v.stride == 2 and v.pad == 1 and v.C == 64 and v.c_phys == 64 and s.c_phys == 32 and not v.fp32):
-            return False
-        if s.parent is not None or s.c_off != 0 or s.ld != s.c_phys:
-            return False
-        users = 0
-        for u in values:
-            if u is v:
-                continue
-            refs = [getattr(u, 'src', None), getattr(u, 'res', None), getattr(u, 'a', None), getattr(u, 'b', None)]
-            refs += [part[0] for part in getattr(u, 'parts', [])] if u.kind == 'concat' else []
-            users += any(r is s for r in refs)
-        return users == 0
-
-    @staticmethod
-    def _junk(plan, grads, n):
-        """Scratch accumulator for a reduction output nobody reads (lives past the parameter slices)."""
-        junk = plan.get('junk')
-        if junk is None or plan['junk_n'] < n:
-            raise RuntimeError('junk accumulator was not reserved')
-        return junk
 
     # --------------------------------------------------------------------------------- execute
     def _get_plan(self, x):

@@ -239,8 +239,47 @@ class FakeLib:
         pitched(d.y, d.pixels, d.c, d.ldy, np.int8)[:] = rnd_away(s * d.inv_scale_sum).clamp(-128, 127).numpy().astype(np.int8)
         return 0
 
+    @staticmethod
+    def _forced_tile_rc(d):
+        """What csrc/conv_igemm.hip yh_conv2d_fwd answers to an explicit tile code BY THE FORM of the descriptor (window, ups, dtype,
+        residual): 0, YH_EINVAL (-1) or YH_EUNSUPPORTED (-3).  The per-shape conditions of a kernel (row counts, K steps,
+        alignment) are not restated: the callers that force a tile keep to them."""
+        t, f16, i8 = d.tile, d.dtype == hiplib.YH_F16, d.dtype == hiplib.YH_I8
+        ring_lds = (21, 22, 24, 25, 26, 27, 31, 32, 34, 35)
+        ring = (1, 2, 3, 4, 5, 6, 11, 12, 14, 15, 16) + ring_lds
+        plain = d.stride == 1 and d.ups == 1
+        if d.ups == 4:
+            return 0 if t in ring_lds else -1
+        if d.ups == 3 and 40 <= t < 50:
+            return -1
+        if t == 71:
+            ok = plain and d.kh == 1 and d.kw == 1 and d.pad == 0 and not _addr(d.res) and not _addr(d.stats_ws) and d.cin == d.cin_k
+            return 0 if ok and d.cout <= 128 and (f16 or i8) else -3
+        if t == 72:
+            ok = d.kh == 3 and d.kw == 3 and d.pad == 1 and d.stride in (1, 2) and d.ups == 1 and not d.out_f32 and (f16 or i8)
+            return 0 if ok else -3
+        if t == 73:
+            ok = plain and d.kh == 1 and d.kw == 1 and d.pad == 0 and not d.out_f32 and d.cin == d.cin_k and (f16 or i8)
+            return 0 if ok else -3
+        if i8:
+            return 0 if t in (21, 24, 25, 26, 27, 64, 65, 66) or (t == 43 and not d.out_f32) else -1
+        if t in ring or t in (51, 52):
+            return 0
+        if t in (41, 42, 43):
+            if t == 43 and (not f16 or d.out_f32):
+                return -3
+            ups_ok = d.ups == 1 or (d.ups == 2 and t != 43)
+            return 0 if d.stride == 1 and ups_ok and d.kh == 3 and d.kw == 3 and d.pad == 1 else -3
+        if 61 <= t <= 69:
+            return 0 if f16 else -1
+        return -1
+
     def yh_conv2d_fwd(self, dref, stream):
         d = dref._obj if hasattr(dref, '_obj') else dref
+        if d.tile != 0:
+            rc = self._forced_tile_rc(d)
+            if rc:
+                return rc
         if d.dtype == hiplib.YH_I8:
             return self._qconv(d)
         npdt = _NP[d.dtype]

@@ -192,7 +192,7 @@ def se(lib, code, x, w1, w2, c, cmap=None):
 
 # ------------------------------------------------------------------------------------------------ int8 (PTQ eval)
 def qconv(lib, x, qw, w_scale, qbias, acc_scale, out_scale, k, stride, pad, act=1, slope=0.1, ups=1, out_f32=False, tile=0,
-          cin=None, x_off=0, y=None, y_off=0, res=None, qadd=None):
+          cin=None, x_off=0, y=None, y_off=0, res=None, qadd=None, res_off=0):
     """x int8 (N,H,W,ldx); qw fp32 (cout,cin,k,k) = int grid * w_scale; qbias fp32 (cout,) real units."""
     N, H, W, ldx = x.shape
     cout, cin_l = qw.shape[0], qw.shape[1]
@@ -212,8 +212,8 @@ def qconv(lib, x, qw, w_scale, qbias, acc_scale, out_scale, k, stride, pad, act=
                  cout=cout_phys, kh=k, kw=k, stride=stride, pad=pad, ldx=ldx, ldr=0, ldy=y.shape[3], cin_k=cin_k, m_pad=m_pad,
                  act=act, slope=slope, ups=ups, out_f32=1 if out_f32 else 0, dtype=hiplib.YH_I8, tile=tile,
                  acc_scale=float(acc_scale), out_scale=float(out_scale))
-    if res is not None:    # fused quantised shortcut: res int8 (N, Ho, Wo, ldr), qadd = (q_rx, q_ra, q_scale_x, q_scale_a, q_inv_scale_sum)
-        d.res, d.ldr = P(res), res.shape[3]
+    if res is not None:    # fused quantised shortcut: res int8 (N, Ho, Wo, ldr) from channel res_off on, qadd = (q_rx, q_ra, q_scale_x, q_scale_a, q_inv_scale_sum)
+        d.res, d.ldr = P(res, res_off), res.shape[3]
         d.q_rx, d.q_ra, d.q_scale_x, d.q_scale_a, d.q_inv_scale_sum = (float(v) for v in qadd)
     rc = lib.yh_conv2d_fwd(C.byref(d), stream())
     assert rc == 0, 'yh_conv2d_fwd(i8) rc=%d' % rc
@@ -309,24 +309,45 @@ def stem_wgrad(lib, code, x, dz, cout, stride=1, pad=1):
     return dw
 
 
-def dgrad(lib, code, dz, w, in_hw, stride, pad, acc=None, fused=False):
+def dgrad(lib, code, dz, w, in_hw, stride, pad, acc=None, fused=False, tile=0, dz_off=0, g_ld=None, g_off=0, out=None, rcs=None):
     """Data gradient through yh_conv2d_fwd on the dgrad weight image (stride 2: four parity phases, ups = 3 scatter, or with
-    ``fused`` all four in one 2x2-tap pass, ups = 4).
-    dz (N,Ho,Wo,cout_phys), w (cout,cin,k,k) fp32 -> dx (N,H,W,cin_phys); ``acc`` (same shape) is accumulated into."""
+    ``fused`` all four in one 2x2-tap pass, ups = 4), in the descriptor form of engine/train_plan.py ``_dgrad``.
+    dz (N,Ho,Wo,lddz): channels [dz_off, dz_off + cout_phys) are read at pitch lddz; w (cout,cin,k,k) fp32.
+    The gradient buffer is (N,H,W,g_ld) and the data gradient owns channels [g_off, g_off + cin_phys) of it: ``acc`` (the WHOLE
+    wide buffer) is passed as both res and y - same pointer, ldr = ldy = g_ld - and accumulated into in place; without it the
+    launch writes into ``out`` (or a fresh buffer filled with 3).  Returns the whole wide buffer.  With ``rcs`` (a list) the
+    return codes of the yh_conv2d_fwd calls are appended to it instead of being asserted to be 0."""
     cout, cin, k, _ = w.shape
-    N, Ho, Wo, cphys = dz.shape
+    N, Ho, Wo, lddz = dz.shape
     H, W = in_hw
     kstep = 32 if code == hiplib.YH_F16 else 16
-    cin_phys = round_up(cin, 8)
+    cin_phys, cphys = round_up(cin, 8), round_up(cout, 8)
+    assert dz_off + cphys <= lddz
     cout_k, dm_pad = round_up(cphys, kstep), round_up(cin_phys, 128)
     wt = torch.empty(dm_pad * k * k * cout_k, device=dz.device, dtype=tdtype(code))
     rc = lib.yh_conv_pack_weights_dgrad(code, P(w), cout, cin, k, k, cout_k, dm_pad, P(wt), stream())
     assert rc == 0, rc
-    dx = acc if acc is not None else torch.full((N, H, W, cin_phys), 3.0, device=dz.device, dtype=dz.dtype)
+    if g_ld is None:
+        g_ld = acc.shape[3] if acc is not None else (out.shape[3] if out is not None else g_off + cin_phys)
+    if acc is not None:
+        dx = acc
+    elif out is not None:
+        dx = out
+    else:
+        dx = torch.full((N, H, W, g_ld), 3.0, device=dz.device, dtype=dz.dtype)
+    assert tuple(dx.shape) == (N, H, W, g_ld) and g_off + cin_phys <= g_ld and dx.is_contiguous() and dz.is_contiguous()
     zero_bias = torch.zeros(dm_pad, device=dz.device, dtype=torch.float32)
-    common = dict(x=P(dz), bias=P(zero_bias), res=P(acc), y=P(dx), n=N, h=Ho, w_in=Wo, cin=cphys, cout=cin_phys, stride=1,
-                  ldx=cphys, ldr=0 if acc is None else cin_phys, ldy=cin_phys, cin_k=cout_k, m_pad=dm_pad, act=0, slope=0.0,
-                  out_f32=0, dtype=code, tile=0)
+    common = dict(x=P(dz, dz_off), bias=P(zero_bias), res=None if acc is None else P(acc, g_off), y=P(dx, g_off), n=N, h=Ho, w_in=Wo,
+                  cin=cphys, cout=cin_phys, stride=1, ldx=lddz, ldr=0 if acc is None else g_ld, ldy=g_ld, cin_k=cout_k,
+                  m_pad=dm_pad, act=0, slope=0.0, out_f32=0, dtype=code, tile=tile)
+
+    def launch(d):
+        rc = lib.yh_conv2d_fwd(C.byref(d), stream())
+        if rcs is not None:
+            rcs.append(int(rc))
+        else:
+            assert rc == 0, 'yh_conv2d_fwd rc=%d' % rc
+
     if stride == 2 and fused:
         from engine.hiplib import PackItem
         fm_pad = round_up(4 * cin_phys, 128)
@@ -337,8 +358,8 @@ def dgrad(lib, code, dz, w, in_hw, stride, pad, acc=None, fused=False):
         rc = lib.yh_pack_batch(P(table), 1, stream())
         assert rc == 0, rc
         zb = torch.zeros(fm_pad, device=dz.device, dtype=torch.float32)
-        call(lib, 'yh_conv2d_fwd', ConvDesc(w=P(img), ho=(H + 1) // 2, wo=(W + 1) // 2, kh=2, kw=2, pad=0, ups=4, y_h=H, y_w=W,
-                                            **dict(common, bias=P(zb), cout=4 * cin_phys, m_pad=fm_pad)))
+        launch(ConvDesc(w=P(img), ho=(H + 1) // 2, wo=(W + 1) // 2, kh=2, kw=2, pad=0, ups=4, y_h=H, y_w=W,
+                        **dict(common, bias=P(zb), cout=4 * cin_phys, m_pad=fm_pad)))
         if dz.is_cuda:
             torch.cuda.synchronize()   # the pack table and image must outlive the launches
         return dx
@@ -355,11 +376,14 @@ def dgrad(lib, code, dz, w, in_hw, stride, pad, acc=None, fused=False):
                 hp, wp = (H - a + 1) // 2, (W - b + 1) // 2
                 if hp <= 0 or wp <= 0:
                     continue
-                call(lib, 'yh_conv2d_fwd', ConvDesc(w=P(img), ho=hp, wo=wp, kh=khp.value, kw=kwp.value, pad=0, ups=3, y_h=H, y_w=W,
-                                                    y_off_h=a, y_off_w=b, **common))
+                launch(ConvDesc(w=P(img), ho=hp, wo=wp, kh=khp.value, kw=kwp.value, pad=0, ups=3, y_h=H, y_w=W, y_off_h=a, y_off_w=b,
+                                **common))
+        if dz.is_cuda:
+            torch.cuda.synchronize()   # the phase images must outlive the launches
         return dx
-    d = ConvDesc(w=P(wt), ho=H, wo=W, kh=k, kw=k, pad=k - 1 - pad, ups=1, **common)
-    call(lib, 'yh_conv2d_fwd', d)
+    launch(ConvDesc(w=P(wt), ho=H, wo=W, kh=k, kw=k, pad=k - 1 - pad, ups=1, **common))
+    if dz.is_cuda:
+        torch.cuda.synchronize()       # the weight image and the zero bias must outlive the launch
     return dx
 
 

@@ -136,6 +136,74 @@ def test_kernel_selection_on_the_headline_network():
     assert lib.yh_conv2d_fwd(C.byref(bad), None) != 0
 
 
+def _dgrad_descs(n, h, w, cin, cout, k, stride, pad, dtype, acc, pitch):
+    """The yh_conv2d_fwd descriptor(s) engine/train_plan.py TrainPlanBuilder._dgrad emits for the data gradient of a conv layer
+    (h, w, cin: its input; the gradient buffer has `pitch` x its channels when it is a slice of a concat parent) -> (form, desc)."""
+    from engine import train as _train
+    round_up = lambda a, b: -(-a // b) * b
+    kstep = 32 if dtype == hiplib.YH_F16 else 16
+    c_phys, s_phys = round_up(cout, 8), round_up(cin, 8)
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ld = pitch * s_phys
+    common = dict(h=ho, w_in=wo, n=n, cin=c_phys, cout=s_phys, stride=1, ldx=c_phys, ldr=ld if acc else 0, ldy=ld,
+                  cin_k=round_up(c_phys, kstep), m_pad=round_up(s_phys, 128), act=0, slope=0.0, out_f32=0, dtype=dtype, tile=0)
+    if stride == 2 and 16 <= s_phys <= _train._FUSED_DGRAD_MAX_CIN and s_phys % 4 == 0:
+        descs = [('fused', hiplib.ConvDesc(ho=(h + 1) // 2, wo=(w + 1) // 2, kh=2, kw=2, pad=0, ups=4, y_h=h, y_w=w,
+                                           **dict(common, cout=4 * s_phys, m_pad=round_up(4 * s_phys, 128))))]
+    elif stride == 2:
+        descs = [('phase', hiplib.ConvDesc(ho=(h - a + 1) // 2, wo=(w - b + 1) // 2, kh=(a + pad) // 2 + 1, kw=(b + pad) // 2 + 1, pad=0, ups=3,
+                                           y_h=h, y_w=w, y_off_h=a, y_off_w=b, **common))
+                 for a in (0, 1) for b in (0, 1) if (h - a + 1) // 2 > 0 and (w - b + 1) // 2 > 0]
+    else:
+        descs = [('plain3' if k == 3 else 'plain1' if k == 1 else 'plain%d' % k,
+                  hiplib.ConvDesc(ho=h, wo=w, kh=k, kw=k, pad=k - 1 - pad, ups=1, **common))]
+    for _, d in descs:
+        d.x = d.w = d.bias = 4096          # any aligned non-null address: the picker reads alignment only
+        d.y = 4096 + (2 if dtype == hiplib.YH_F16 else 4) * (ld - s_phys)      # the last slice of the parent
+        d.res = d.y if acc else None       # accumulate: the planner passes the gradient itself as the residual
+    return descs
+
+
+def test_data_gradient_kernels_are_the_tested_ones():
+    """Every data gradient of every shipped cfg (bench batch, the cfg's own size; YOLOv3 also at 608 / batch 64), in write and in
+    accumulate mode, fp16 and fp32, contiguous and as a slice of a wider gradient buffer: the kernel yh_conv2d_tile chooses for it must
+    be one tests/test_gpu_dgrad_forms.py exercises IN DATA-GRADIENT FORM (its ACCEPTED table).  No tile number is pinned - the picker
+    may be retuned - but a data gradient must not land on a kernel that conformance file does not run (host code: no GPU needed)."""
+    import glob
+    sys.path.insert(0, os.path.join(REPO, 'tests', 'golden'))
+    try:
+        from make_golden_wgrad_selection import conv_layers
+    finally:
+        sys.path.pop(0)
+    import conftest
+    import test_gpu_dgrad_forms as forms
+    lib = hiplib.load()
+    cfgs = [(p, None, 32 if 'yolov4' in os.path.basename(p) else 64) for p in sorted(glob.glob(os.path.join(conftest.PKG, 'cfg', '**', '*.cfg'), recursive=True))]
+    cfgs.append((os.path.join(conftest.PKG, 'cfg', 'yolov3', 'yolov3.cfg'), 608, 64))
+    assert len(cfgs) > 5
+    seen, chosen = set(), {}
+    for path, size, batch in cfgs:
+        for (h, w, cin, cout, k, stride, pad) in conv_layers(path, size):
+            if cin == 3 or (h, w, cin, cout, k, stride, pad, batch) in seen:      # no data gradient into the image
+                continue
+            seen.add((h, w, cin, cout, k, stride, pad, batch))
+            assert stride in (1, 2), (path, stride)
+            for dtype in (hiplib.YH_F16, hiplib.YH_F32):
+                for acc in (False, True):
+                    for pitch in (1, 2):
+                        for form, d in _dgrad_descs(batch, h, w, cin, cout, k, stride, pad, dtype, acc, pitch):
+                            tile = int(lib.yh_conv2d_tile(C.byref(d)))
+                            what = (os.path.basename(path), h, w, cin, cout, k, stride, dtype, acc, pitch, form, tile)
+                            assert form in forms.ACCEPTED, what
+                            if form == 'fused' and not 21 <= tile <= 35:
+                                tile = 24      # yh_conv2d_fwd: only the LDS-DMA ring kernels carry the four-phase scatter
+                            assert tile in forms.ACCEPTED[form] and tile != 0, what
+                            assert dtype == hiplib.YH_F16 or tile in forms.F32_TILES, what
+                            assert not (tile == 71 and acc), what
+                            chosen.setdefault(form, set()).add(tile)
+    assert len(seen) > 100 and set(chosen) == set(forms.FORMS), (len(seen), sorted(chosen))
+
+
 def _roll_workspace(r):
     """Floats of partial tiles conv_wgrad_roll_kernel writes for a 3x3 / s1 row (csrc/conv_wgrad_roll.hip, wgrad_roll_geometry): one
     128 x [9 x 64] tile per (split, tile); 256 / tiles splits of the 32-position steps of the padded pixel space, at least 8 steps each."""
